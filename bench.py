@@ -6,7 +6,15 @@ consistency forward (eval BN) + consistency loss + backward, clip + SGD step, EM
 libssseg.so kernels, bf16 activations/weights with fp32 accumulation, fp32 master weights and EMA.
 Inputs are synthetic and pre-generated in HBM (8 batches cycled); weights random-init.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--size S] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--size S] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: build, warm up (at least two eager steps: the first tunes
+the conv geometries, the second builds the teacher's BN fold table), capture the step, time K steps, print the line.
+--full adds every other leg to the same line: the instrumented step behind 'roofline', the eagerly issued steps
+('eager_n1'), the fp32 parity mode ('fp32_mode', unless --no-fp32), the CPU baseline and the mIoU parity leg
+('cpu_baseline', 'parity', unless --no-cpu-baseline).  --dump-outputs DIR writes what the last timed step computed
+(dump_outputs below) as DIR/<name>.npy; model, data and CowMix draws are seeded, so two builds run with the same
+arguments can be compared array by array.
 
 N>1: when WORLD_SIZE is not set, bench.py itself starts torch.distributed.run as a child process
 (before any GPU call) with one rank per GPU on RCCL; under an external launcher it joins as a rank.
@@ -67,6 +75,29 @@ def pmc_mfma():
                                                           'cycles))'}
     except (OSError, KeyError, ValueError, TypeError):
         return None
+
+
+DUMP_SAMPLE = 4 * 2 ** 20       # elements kept per state file of --dump-outputs (2 files x 16 MiB, float32)
+DUMP_SAMPLE_SEED = 2718
+
+
+def dump_outputs(path, model, teacher, rec):
+    """--dump-outputs: what the caller of the last timed step holds after it, as float32 .npy files.  losses.npy: the
+    step's return value (supervised loss, consistency loss, CowMix mask mean).  student_state.npy / teacher_state.npy:
+    the state the step updated in place (clip + SGD, BN running statistics, EMA) -- every floating-point state_dict
+    entry flattened in state_dict order; a model with more than DUMP_SAMPLE elements is cut to a fixed seeded sample of
+    element positions (sorted; the same positions on every run of the same model)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, 'losses.npy'), torch.stack([t.detach().float().reshape(()) for t in rec]).cpu().numpy())
+    for name, m in (('student_state', model), ('teacher_state', teacher)):
+        m = m.module if hasattr(m, 'module') else m
+        flat = torch.cat([v.detach().float().reshape(-1) for v in m.state_dict().values() if v.is_floating_point()])
+        if flat.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(DUMP_SAMPLE_SEED)
+            idx = torch.randint(flat.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(path, name + '.npy'), flat.cpu().numpy())
 
 
 def build(batch, size, device):
@@ -344,6 +375,8 @@ def timed_run(args, world, rank, device, dtype, probe=True, eager_n1=False):
         return el
 
     elapsed = timed_steps(one_step, args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, teacher, recs[-1])
     eager = None
     if graph is not None and world == 1 and eager_n1:
         # the same model continued for the same number of steps with every launch issued from Python
@@ -365,8 +398,13 @@ def main():
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--batch', type=int, default=16)
     ap.add_argument('--size', type=int, default=512)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-fp32', action='store_true', help='skip the secondary fp32 (parity-mode) record')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy (see dump_outputs)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the legs beside the headline figure: roofline probe, eager_n1, fp32_mode, '
+                         'cpu_baseline and parity')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the cpu_baseline and parity records')
+    ap.add_argument('--no-fp32', action='store_true', help='with --full: skip the secondary fp32 (parity-mode) record')
     ap.add_argument('--no-graph', dest='graph', action='store_false',
                     help='issue every launch from Python each step instead of replaying the captured HIP graph')
     args = ap.parse_args()
@@ -392,15 +430,13 @@ def main():
     from ssseg import comm as scomm
     from ssseg import tune
     elapsed, rows, live, model, graphed, eager, tune_digests = timed_run(args, world, rank, device, torch.bfloat16,
-                                                                         eager_n1=(world == 1))
+                                                                         probe=args.full,
+                                                                         eager_n1=(world == 1 and args.full))
     finite = bool(torch.isfinite(live).all())
     if not finite:
         raise RuntimeError(f'bench: non-finite loss in the timed steps (rank {rank}): {live.tolist()}')
-    conv_ms = sum(r[0].elapsed_time(r[1]) for r in rows)
-    conv_flops = sum(r[2] for r in rows)
     images = world * args.batch * args.steps
     value = images / elapsed
-    achieved = conv_flops / (conv_ms / 1e3)
     result = {
         'metric': 'images/sec (UNet-R50 512x512 bs=16/GPU, mean-teacher + CowMix semi-supervised training step)',
         'value': round(value, 3), 'unit': 'images/sec', 'n_gpus': world, 'steps': args.steps,
@@ -410,12 +446,6 @@ def main():
                                'mean-teacher + CowMix step (BCE sup loss w=0.5, consistency w=10, SGD m=0.9)',
                    'global_batch': world * args.batch, 'per_gpu_batch': args.batch, 'image_size': args.size,
                    'parallelism': f'dp{world}', 'confidence_threshold': THRESHOLD},
-        'roofline': {'bound': 'mfma', 'kernel': 'conv engine (igemm fwd/dgrad/ConvT + wgrad), all launches of one step',
-                     'achieved': round(achieved / 1e12, 2), 'peak': BF16_DENSE_PEAK / 1e12, 'unit': 'TFLOP/s',
-                     'frac': round(achieved / BF16_DENSE_PEAK, 4), 'traffic': pmc_traffic(),
-                     'traffic_unit': 'HBM bytes per step, conv engine (rocprofv3 PMC, ' + os.path.relpath(PMC_PROFILE, ROOT) + ')',
-                     'conv_ms_per_step': round(conv_ms, 3), 'conv_gflop_per_step': round(conv_flops / 1e9, 1),
-                     'launches_per_step': len(rows), 'mfma_pmc': pmc_mfma()},
         'execution': ('HIP graph replay of the captured step (ssseg.graph.StepGraph), one per step' if graphed[0]
                       else 'eager launches from Python (the host reducer issues the bucket all-reduces)'
                       + (f'; capture failed: {graphed[1]}' if graphed[1] else '')),
@@ -431,15 +461,26 @@ def main():
                      'unsup_loss_last': round(float(live[-1, 1]), 6),
                      'cm_mean_avg': round(float(live[:, 2].mean()), 4)},
     }
+    if args.full:     # the instrumented step of timed_run: HIP events around every conv-engine launch
+        conv_ms = sum(r[0].elapsed_time(r[1]) for r in rows)
+        conv_flops = sum(r[2] for r in rows)
+        achieved = conv_flops / (conv_ms / 1e3)
+        result['roofline'] = {
+            'bound': 'mfma', 'kernel': 'conv engine (igemm fwd/dgrad/ConvT + wgrad), all launches of one step',
+            'achieved': round(achieved / 1e12, 2), 'peak': BF16_DENSE_PEAK / 1e12, 'unit': 'TFLOP/s',
+            'frac': round(achieved / BF16_DENSE_PEAK, 4), 'traffic': pmc_traffic(),
+            'traffic_unit': 'HBM bytes per step, conv engine (rocprofv3 PMC, ' + os.path.relpath(PMC_PROFILE, ROOT) + ')',
+            'conv_ms_per_step': round(conv_ms, 3), 'conv_gflop_per_step': round(conv_flops / 1e9, 1),
+            'launches_per_step': len(rows), 'mfma_pmc': pmc_mfma()}
     if eager is not None:
         result['eager_n1'] = {'value': round(world * args.batch * args.steps / eager, 3), 'unit': 'images/sec',
                               'ms_per_step': round(eager / args.steps * 1e3, 3), 'steps': args.steps,
                               'note': 'the same N=1 workload, every launch issued from Python instead of the '
                                       'captured-step replay'}
-    if rank == 0 and world == 1 and not args.no_fp32:
+    if args.full and rank == 0 and world == 1 and not args.no_fp32:
         try:
-            f_el, _, f_live, _, _, _, _ = timed_run(argparse.Namespace(**dict(vars(args), steps=min(args.steps, 5), warmup=2)),
-                                        world, rank, device, torch.float32, probe=False)
+            f_args = argparse.Namespace(**dict(vars(args), steps=min(args.steps, 5), warmup=2, dump_outputs=None))
+            f_el, _, f_live, _, _, _, _ = timed_run(f_args, world, rank, device, torch.float32, probe=False)
             n = min(args.steps, 5)
             result['fp32_mode'] = {'value': round(args.batch * n / f_el, 3), 'unit': 'images/sec',
                                    'ms_per_step': round(f_el / n * 1e3, 3), 'steps': n,
@@ -447,7 +488,7 @@ def main():
                                    'note': 'same C2 step in the fp32 parity mode (the reference arithmetic)'}
         except Exception as exc:  # report, never hide
             result['fp32_mode'] = {'error': repr(exc)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             result['cpu_baseline'] = cpu_baseline(args.size)
         except Exception as exc:  # report, never hide

@@ -74,8 +74,33 @@ def save(name, **arrays):
             v = v.detach().cpu().numpy()
         out[k] = np.asarray(v)
     out['torch_version'] = np.asarray(META['torch_version'])
-    np.savez_compressed(path, **out)
-    print(f'wrote {name}: {os.path.getsize(path) / 1024:.1f} KiB')
+    for part, keys in enumerate(split_keys(out)):
+        p = path if part == 0 else f'{path[:-4]}.part{part}.npz'
+        np.savez_compressed(p, **{k: out[k] for k in keys})
+        assert os.path.getsize(p) <= PART_LIMIT, (p, os.path.getsize(p))
+        print(f'wrote {os.path.basename(p)}: {os.path.getsize(p) / 1024:.1f} KiB')
+
+
+PART_LIMIT = 2 ** 20    # no committed file over 1 MiB: a larger fixture goes into name.npz, name.part1.npz, ...
+
+
+def split_keys(arrays, budget=PART_LIMIT - 96 * 1024):
+    """The keys of one fixture, in order, cut into runs whose compressed size stays under `budget` each (estimated per
+    array: its deflated .npy bytes plus the zip entry's two headers); tests/conftest.py golden() reads the parts back
+    as one mapping in the same key order."""
+    import io
+    import zlib
+    parts, size = [[]], 0
+    for k, v in arrays.items():
+        buf = io.BytesIO()
+        np.save(buf, v, allow_pickle=False)
+        n = len(zlib.compress(buf.getvalue())) + 2 * len(k) + 160
+        if parts[-1] and size + n > budget:
+            parts.append([])
+            size = 0
+        parts[-1].append(k)
+        size += n
+    return parts
 
 
 def state_arrays(prefix, module):

@@ -12,8 +12,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('trace')
     ap.add_argument('--steps', type=int, default=7)
-    ap.add_argument('--skip-last', type=int, default=0, help='steps at the end to leave out (e.g. bench.py\'s eager_n1 '
-                    'steps after the graph-replayed ones)')
+    ap.add_argument('--skip-last', type=int, default=0, help='steps at the end to leave out (e.g. the eager_n1 steps that '
+                    'bench.py --full runs after the graph-replayed ones)')
     a = ap.parse_args()
     rows = sorted((int(r['Start_Timestamp']), int(r['End_Timestamp']), r['Kernel_Name'])
                   for r in csv.DictReader(open(a.trace)))

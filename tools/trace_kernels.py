@@ -20,7 +20,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('trace')
     ap.add_argument('--steps', type=int, default=7)
-    ap.add_argument('--skip-last', type=int, default=0, help="steps at the end to leave out (bench.py's eager_n1 steps)")
+    ap.add_argument('--skip-last', type=int, default=0, help="steps at the end to leave out (the eager_n1 steps of bench.py --full)")
     a = ap.parse_args()
     rows = [(r['Kernel_Name'], int(r['Start_Timestamp']), int(r['End_Timestamp'])) for r in csv.DictReader(open(a.trace))]
     sgd = sorted(s for n, s, e in rows if 'sgd_kernel' in n)
