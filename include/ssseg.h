@@ -223,6 +223,103 @@ int ssseg_rmi_bwd(const float* logits, int64_t N, int64_t C, int64_t H, int64_t 
                   float* grad_out, void* ws, size_t ws_bytes, ssseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The other losses of the reference's losses.py (csrc/seglosses.hip).  x, t: contiguous fp32 [B,C,HW] (targets may
+ * be soft), 1 <= C <= 64 for the per-pixel softmax family (SSSEG_EINVAL otherwise, checked on the host before any
+ * launch, like null pointers).  Reductions: per-block fp64 partials + one final block in the caller's workspace
+ * (bitwise reproducible, no floating-point atomics).  Every backward recomputes from (x, t), reads the upstream
+ * gradient gout from device memory and writes gx = gout * d loss / d x; the backwards that take `ws` read what the
+ * forward with the same arguments left in the same workspace (kept unchanged in between).
+ * ------------------------------------------------------------------------------------------- */
+enum { SSSEG_RED_NONE = 0, SSSEG_RED_MEAN = 1, SSSEG_RED_SUM = 2 };
+enum { SSSEG_LOSS_REDUCE = 0,      /* CE, Focal, the entropies, BCE 'sum': one scalar reduction */
+       SSSEG_LOSS_OHEM = 1, SSSEG_LOSS_NFL = 2, SSSEG_LOSS_DICE_LOGITS = 3,
+       SSSEG_LOSS_DICE_PROB = 4    /* (B, 1, n) */ };
+/* Workspace bytes of the loss `kind` at [B,C,HW]; 0 for an unknown kind or an empty shape. */
+size_t ssseg_segloss_workspace_bytes(int kind, int64_t B, int64_t C, int64_t HW);
+
+/* DenseCrossEntropyLossWithLogits (losses.py:25-39): l[b,pix] = -sum_c t_c * log_softmax(x)_c.
+ * SSSEG_RED_MEAN: out[0] = mean over B*HW.  SSSEG_RED_NONE: out [B,HW] (no workspace needed). */
+int ssseg_ce_fwd(const float* x, const float* t, int64_t B, int64_t C, int64_t HW, int reduction, float* out,
+                 void* ws, size_t ws_bytes, ssseg_stream_t stream);
+/* gx_c = g * (softmax(x)_c * sum_k t_k - t_c); g = gout[0] / (B*HW) (mean) or gout[b,pix] (none). */
+int ssseg_ce_bwd(const float* x, const float* t, int64_t B, int64_t C, int64_t HW, int reduction, const float* gout,
+                 float* gx, ssseg_stream_t stream);
+
+/* OhemCrossEntropy (losses.py:51-69): pred = softmax(x) at argmax_c t (first maximum), threshold =
+ * max(sorted(pred)[min(min_kept, B*HW - 1)], thresh), out[0] = mean CE over the pixels with pred < threshold
+ * (NaN when none).  The order statistic is found on the device (no host sync) by an exact radix select over the
+ * fp32 bit pattern of pred: four 8-bit histogram passes (integer counts: deterministic), no sort.  The forward
+ * leaves pred per pixel, the threshold (double 0 of ws) and the kept count (double 1 of ws) for the backward; no
+ * gradient flows through the selection. */
+int ssseg_ohem_fwd(const float* x, const float* t, int64_t B, int64_t C, int64_t HW, float thresh, int64_t min_kept,
+                   float* out, void* ws, size_t ws_bytes, ssseg_stream_t stream);
+int ssseg_ohem_bwd(const float* x, const float* t, int64_t B, int64_t C, int64_t HW, const float* gout, float* gx,
+                   const void* ws, size_t ws_bytes, ssseg_stream_t stream);
+
+/* FocalLoss (losses.py:72-90), n elements: out[0] = mean((1 - p_t)^gamma * (t alpha + (1-t)(1-alpha)) * bce(x, t)),
+ * p_t = t p + (1-t)(1-p), p = sigmoid(x).  Backward: autograd of that expression (valid for soft targets). */
+int ssseg_focal_fwd(const float* x, const float* t, int64_t n, double alpha, double gamma, float* out, void* ws,
+                    size_t ws_bytes, ssseg_stream_t stream);
+int ssseg_focal_bwd(const float* x, const float* t, int64_t n, double alpha, double gamma, const float* gout,
+                    float* gx, ssseg_stream_t stream);
+
+/* NormalizedFocalLossSigmoid (losses.py:93-151) with detach_delimeter=True and a scalar weight. */
+typedef struct ssseg_nfl_params {
+  double alpha, gamma, eps, scale, weight, ignore_label;
+  int32_t from_logits, size_average;
+} ssseg_nfl_params;
+/* x, label [B,C,HW]; params_host is read on the host.  pt = pred or 1 - pred by label > 0 (1 where label ==
+ * ignore_label), beta = (1 - pt)^gamma, mult[b,c] = HW / (sum_HW beta + eps) (a constant of the backward),
+ * loss = -alpha_t beta mult log(min(pt + eps, 1)) * weight on label != ignore_label, summed per sample and divided by
+ * (#label != ignore_label + eps) if size_average; out [B] = scale * that.  k_sum (nullable, 1 float): the EMA
+ * k = 0.9 k + 0.1 mean_b(mean_c mult) over the samples without a -1 label, unchanged if there are none. */
+int ssseg_nfl_fwd(const float* x, const float* label, int64_t B, int64_t C, int64_t HW,
+                  const ssseg_nfl_params* params_host, float* out, float* k_sum, void* ws, size_t ws_bytes,
+                  ssseg_stream_t stream);
+/* gout [B] */
+int ssseg_nfl_bwd(const float* x, const float* label, int64_t B, int64_t C, int64_t HW,
+                  const ssseg_nfl_params* params_host, const float* gout, float* gx, const void* ws, size_t ws_bytes,
+                  ssseg_stream_t stream);
+
+/* DiceWithLogitsLoss (losses.py:157-167): p = softmax(x); per (b,c) I = sum p t, K = sum p + sum t,
+ * dice = (2I + 1)/(K + 1), mask = sum t > 1; out[0] = 1 - mean_b(sum_c dice mask / sum_c mask) (NaN when a sample
+ * has no class present).  The forward leaves the per-(b,c) coefficients of d loss / d p in ws; the backward is one
+ * pass through the softmax Jacobian. */
+int ssseg_dice_logits_fwd(const float* x, const float* t, int64_t B, int64_t C, int64_t HW, float* out, void* ws,
+                          size_t ws_bytes, ssseg_stream_t stream);
+int ssseg_dice_logits_bwd(const float* x, const float* t, int64_t B, int64_t C, int64_t HW, const float* gout,
+                          float* gx, const void* ws, size_t ws_bytes, ssseg_stream_t stream);
+
+/* dice_loss / log_dice_loss (losses.py:221-236) on probabilities p, t [B,n] (n = C*H*W):
+ * r_b = (2 sum p t + 1)/(sum (p + t) + 1); out [B] = 1 - r (log_mode 0) or (-log r)^gamma (log_mode 1).
+ * gout [B]; gx = d loss / d p. */
+int ssseg_dice_prob_fwd(const float* p, const float* t, int64_t B, int64_t n, int log_mode, float gamma, float* out,
+                        void* ws, size_t ws_bytes, ssseg_stream_t stream);
+int ssseg_dice_prob_bwd(const float* t, int64_t B, int64_t n, int log_mode, float gamma, const float* gout,
+                        float* gx, const void* ws, size_t ws_bytes, ssseg_stream_t stream);
+
+/* binary_entropy_loss (losses.py:253-257), as written: p = sigmoid(x), out[0] = -mean(p log p + (1-p) log(1-p)) / 2
+ * (NaN where the fp32 sigmoid is exactly 0 or 1). */
+int ssseg_binary_entropy_fwd(const float* x, int64_t n, float* out, void* ws, size_t ws_bytes,
+                             ssseg_stream_t stream);
+int ssseg_binary_entropy_bwd(const float* x, int64_t n, const float* gout, float* gx, ssseg_stream_t stream);
+/* entropy_loss (losses.py:260-264): out[0] = mean over B*HW of -sum_c softmax(x)_c log_softmax(x)_c. */
+int ssseg_entropy_fwd(const float* x, int64_t B, int64_t C, int64_t HW, float* out, void* ws, size_t ws_bytes,
+                      ssseg_stream_t stream);
+int ssseg_entropy_bwd(const float* x, int64_t B, int64_t C, int64_t HW, const float* gout, float* gx,
+                      ssseg_stream_t stream);
+
+/* binary_cross_entropy_with_logits with reduction 'none' (out [n], gout [n]) or 'sum' (out[0], gout[0])
+ * (losses.py:41-48); 'mean' is ssseg_bce_logits_fwd. */
+int ssseg_bce_logits_red_fwd(const float* x, const float* t, int64_t n, int reduction, float* out, void* ws,
+                             size_t ws_bytes, ssseg_stream_t stream);
+int ssseg_bce_logits_red_bwd(const float* x, const float* t, int64_t n, int reduction, const float* gout, float* gx,
+                             ssseg_stream_t stream);
+
+/* smooth_labels (losses.py:267-268): out = t * a + b with a = 1 - alpha, b = alpha / C (each operation rounded). */
+int ssseg_smooth_labels(const float* t, float* out, int64_t n, float a, float b, ssseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Teacher EMA and optimiser over flat parameter arenas
  * ------------------------------------------------------------------------------------------- */
 

@@ -1,16 +1,25 @@
-"""Losses — drop-in for the hot-path part of reference losses.py, on the MI355X kernels.
+"""Losses — drop-in for the reference's losses.py, on the MI355X kernels.
 
   CalculateLoss                           losses.py:8-22   (bilinear resize of each prediction + weighted sum)
-  DenseBinaryCrossEntropyLossWithLogits   losses.py:41-48  (reduction='mean')
+  DenseCrossEntropyLossWithLogits         losses.py:25-39  (reduction 'mean' / 'none', soft targets)
+  DenseBinaryCrossEntropyLossWithLogits   losses.py:41-48  (reduction 'mean' / 'sum' / 'none')
+  OhemCrossEntropy                        losses.py:51-69  (order statistic by a device radix select, no host sync)
+  FocalLoss                               losses.py:72-90
+  NormalizedFocalLossSigmoid              losses.py:93-151 (detach_delimeter=True, scalar weight; _k_sum on the device)
+  DiceWithLogitsLoss                      losses.py:157-167
+  get_dims_with_exclusion                 losses.py:213-218
+  dice_loss, log_dice_loss                losses.py:221-236
   binary_lovasz_loss_with_logits          losses.py:239-250
+  binary_entropy_loss, entropy_loss       losses.py:253-264
+  smooth_labels                           losses.py:267-268
   RMILoss                                 losses.py:271-592 (the default-config loss, configs/default_config.py:147;
                                           sigmoid form, rmi_pool 'avg' / 'none', rmi_radius 1-3)
-Out of scope (not in the hot path / BASELINE configs): Focal, OHEM, Dice, NormalizedFocal, entropy
-(losses.py:51-230) — calling them raises NotImplementedError.
+Every loss runs in csrc/eltwise.hip, lovasz.hip, rmi.hip or seglosses.hip; there is no framework fallback.
 """
 import torch
 import torch.nn as nn
 
+from ssseg import native as N
 from ssseg import ops
 
 
@@ -31,15 +40,123 @@ class CalculateLoss:
         return total if total is not None else 0
 
 
-class DenseBinaryCrossEntropyLossWithLogits(nn.Module):
+class DenseCrossEntropyLossWithLogits(nn.Module):
     def __init__(self, reduction='mean'):
         super().__init__()
-        if reduction != 'mean':
-            raise NotImplementedError('only reduction="mean" has a kernel (the hot-path configuration)')
         self.reduction = reduction
 
     def forward(self, input, target):
-        return ops.bce_with_logits_mean(input, target)
+        if self.reduction not in ('mean', 'none'):
+            raise ValueError(f'incorrect value of reduction param: `{self.reduction}`')
+        return ops.dense_cross_entropy(input, target, self.reduction)
+
+
+class DenseBinaryCrossEntropyLossWithLogits(nn.Module):
+    def __init__(self, reduction='mean'):
+        super().__init__()
+        self.reduction = reduction
+
+    def forward(self, input, target):
+        if self.reduction == 'mean':
+            return ops.bce_with_logits_mean(input, target)
+        if self.reduction not in ('sum', 'none'):
+            raise ValueError(f'{self.reduction} is not a valid value for reduction')
+        return ops.bce_with_logits(input, target, self.reduction)
+
+
+class OhemCrossEntropy(nn.Module):
+    def __init__(self, thres=0.7, min_kept=100000):
+        super().__init__()
+        self.thresh = thres
+        self.min_kept = max(1, min_kept)
+        self.criterion = DenseCrossEntropyLossWithLogits(reduction='none')
+
+    def forward(self, logits, target):
+        return ops.ohem_cross_entropy(logits, target, self.thresh, self.min_kept)
+
+
+class FocalLoss(nn.Module):
+    def __init__(self, alpha=0.25, gamma=2.0):
+        super().__init__()
+        self.alpha = alpha
+        self.gamma = gamma
+
+    def forward(self, inputs, targets):
+        return ops.focal_loss(inputs, targets, self.alpha, self.gamma)
+
+
+class NormalizedFocalLossSigmoid(nn.Module):
+    """losses.py:93-151.  The reference keeps `_k_sum` as a host float and reads two tensors back per call; here it is
+    a device scalar that the final kernel of the forward updates under the same rule (`float(loss._k_sum)` works), so
+    the forward never synchronises.  detach_delimeter=False (on which the reference itself raises, losses.py:136) and
+    a tensor `weight` are refused at construction."""
+
+    def __init__(self, axis=-1, alpha=0.25, gamma=2, from_logits=False, batch_axis=0, weight=None, size_average=True,
+                 detach_delimeter=True, eps=1e-12, scale=1.0, ignore_label=-1):
+        super().__init__()
+        if not detach_delimeter:
+            raise NotImplementedError('NormalizedFocalLossSigmoid: detach_delimeter=False (the reference raises on it)')
+        if isinstance(weight, torch.Tensor):
+            raise NotImplementedError('NormalizedFocalLossSigmoid: a tensor `weight` (the kernel takes a scalar)')
+        self._axis = axis
+        self._alpha = alpha
+        self._gamma = gamma
+        self._ignore_label = ignore_label
+        self._weight = weight if weight is not None else 1.0
+        self._batch_axis = batch_axis
+        self._scale = scale
+        self._from_logits = from_logits
+        self._eps = eps
+        self._size_average = size_average
+        self._detach_delimeter = detach_delimeter
+        self._k_sum = 0
+
+    def forward(self, pred, label, sample_weight=None):
+        if not isinstance(self._k_sum, torch.Tensor):
+            self._k_sum = torch.full((), float(self._k_sum), device=pred.device, dtype=torch.float32)
+        params = N.NflParams(self._alpha, self._gamma, self._eps, self._scale, self._weight, self._ignore_label,
+                             int(bool(self._from_logits)), int(bool(self._size_average)))
+        return ops.normalized_focal_loss(pred, label, params, self._k_sum)
+
+    def log_states(self, sw, name, global_step):
+        sw.add_scalar(tag=name + '_k', value=float(self._k_sum), global_step=global_step)
+
+
+class DiceWithLogitsLoss(nn.Module):
+    def forward(self, input, target):
+        return ops.dice_with_logits(input, target)
+
+
+def get_dims_with_exclusion(dim, exclude=None):
+    dims = list(range(dim))
+    if exclude is not None:
+        dims.remove(exclude)
+    return dims
+
+
+def dice_loss(input, target):
+    """losses.py:221-227 on probabilities: per-sample 1 - (2 I + 1) / (K + 1)."""
+    return ops.dice_prob(input, target, log_mode=False)
+
+
+def log_dice_loss(input, target, gamma=1.0):
+    """losses.py:230-236: per-sample (-log((2 I + 1) / (K + 1))) ** gamma."""
+    return ops.dice_prob(input, target, log_mode=True, gamma=gamma)
+
+
+def binary_entropy_loss(input):
+    """losses.py:253-257, literally: sigmoid, then log (NaN where the fp32 sigmoid saturates, as in the reference)."""
+    return ops.binary_entropy(input)
+
+
+def entropy_loss(input):
+    """losses.py:260-264."""
+    return ops.entropy(input)
+
+
+def smooth_labels(target, alpha=0.1):
+    """losses.py:267-268: target * (1 - alpha) + alpha / C."""
+    return ops.smooth_labels(target, alpha)
 
 
 def binary_lovasz_loss_with_logits(input, target):
@@ -86,14 +203,3 @@ class RMILoss(nn.Module):
 
     def forward(self, logits_4D, labels_4D):
         return ops.rmi_loss(logits_4D, labels_4D, self.num_classes, self.rmi_radius, *self.pool_params())
-
-
-def _out_of_scope(name):
-    def f(*a, **k):
-        raise NotImplementedError(f'losses.{name} is outside the MI355X hot path (SURVEY §2.1 row 3)')
-    return f
-
-
-for _n in ('DenseCrossEntropyLossWithLogits', 'OhemCrossEntropy', 'FocalLoss', 'DiceWithLogitsLoss',
-           'NormalizedFocalLossSigmoid', 'binary_entropy_loss', 'entropy_loss', 'log_dice_loss'):
-    globals()[_n] = _out_of_scope(_n)

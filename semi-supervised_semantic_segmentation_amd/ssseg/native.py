@@ -67,6 +67,27 @@ SIGS = {
     'ssseg_rmi_workspace_bytes': (sz, [i64] * 9),
     'ssseg_rmi_fwd': (i32, [vp, vp] + [i64] * 9 + [i32, vp, vp, sz, vp]),
     'ssseg_rmi_bwd': (i32, [vp] + [i64] * 9 + [vp, vp, vp, sz, vp]),
+    # the other reference losses (csrc/seglosses.hip)
+    'ssseg_segloss_workspace_bytes': (sz, [i32, i64, i64, i64]),
+    'ssseg_ce_fwd': (i32, [vp, vp, i64, i64, i64, i32, vp, vp, sz, vp]),
+    'ssseg_ce_bwd': (i32, [vp, vp, i64, i64, i64, i32, vp, vp, vp]),
+    'ssseg_ohem_fwd': (i32, [vp, vp, i64, i64, i64, f32, i64, vp, vp, sz, vp]),
+    'ssseg_ohem_bwd': (i32, [vp, vp, i64, i64, i64, vp, vp, vp, sz, vp]),
+    'ssseg_focal_fwd': (i32, [vp, vp, i64, f64, f64, vp, vp, sz, vp]),
+    'ssseg_focal_bwd': (i32, [vp, vp, i64, f64, f64, vp, vp, vp]),
+    'ssseg_nfl_fwd': (i32, [vp, vp, i64, i64, i64, vp, vp, vp, vp, sz, vp]),
+    'ssseg_nfl_bwd': (i32, [vp, vp, i64, i64, i64, vp, vp, vp, vp, sz, vp]),
+    'ssseg_dice_logits_fwd': (i32, [vp, vp, i64, i64, i64, vp, vp, sz, vp]),
+    'ssseg_dice_logits_bwd': (i32, [vp, vp, i64, i64, i64, vp, vp, vp, sz, vp]),
+    'ssseg_dice_prob_fwd': (i32, [vp, vp, i64, i64, i32, f32, vp, vp, sz, vp]),
+    'ssseg_dice_prob_bwd': (i32, [vp, i64, i64, i32, f32, vp, vp, vp, sz, vp]),
+    'ssseg_binary_entropy_fwd': (i32, [vp, i64, vp, vp, sz, vp]),
+    'ssseg_binary_entropy_bwd': (i32, [vp, i64, vp, vp, vp]),
+    'ssseg_entropy_fwd': (i32, [vp, i64, i64, i64, vp, vp, sz, vp]),
+    'ssseg_entropy_bwd': (i32, [vp, i64, i64, i64, vp, vp, vp]),
+    'ssseg_bce_logits_red_fwd': (i32, [vp, vp, i64, i32, vp, vp, sz, vp]),
+    'ssseg_bce_logits_red_bwd': (i32, [vp, vp, i64, i32, vp, vp, vp]),
+    'ssseg_smooth_labels': (i32, [vp, vp, i64, f32, f32, vp]),
     'ssseg_prob_onehot': (i32, [vp, i64, i64, vp, vp, vp]),
     'ssseg_seg_metrics': (i32, [vp, I64P, i64, i64, vp, I64P, i64, i64, i64, vp, vp, vp, vp]),
     'ssseg_ema_update': (i32, [vp, vp, i64, f64, vp]),
@@ -185,6 +206,16 @@ class ConvEpilogue(ctypes.Structure):
     _fields_ = [('scale', ctypes.c_void_p), ('shift', ctypes.c_void_p), ('residual', ctypes.c_void_p),
                 ('ldr', ctypes.c_int64), ('aux', ctypes.c_void_p), ('relu', ctypes.c_int32), ('slope', ctypes.c_float),
                 ('stats', ctypes.c_void_p), ('stats_ld', ctypes.c_int64), ('stats_rows', ctypes.c_void_p)]
+
+
+class NflParams(ctypes.Structure):
+    """Mirror of ssseg_nfl_params (include/ssseg.h)."""
+    _fields_ = [(n, ctypes.c_double) for n in ('alpha', 'gamma', 'eps', 'scale', 'weight', 'ignore_label')] + \
+               [('from_logits', ctypes.c_int32), ('size_average', ctypes.c_int32)]
+
+
+RED_NONE, RED_MEAN, RED_SUM = 0, 1, 2
+LOSS_REDUCE, LOSS_OHEM, LOSS_NFL, LOSS_DICE_LOGITS, LOSS_DICE_PROB = 0, 1, 2, 3, 4
 
 
 class VCat(ctypes.Structure):

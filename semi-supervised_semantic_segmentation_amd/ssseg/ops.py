@@ -2,6 +2,7 @@
 
 Each function documents the reference call site it replaces.  Inputs must be HIP tensors.
 """
+import ctypes
 import os
 
 import torch
@@ -357,6 +358,310 @@ def rmi_loss(logits, target, num_classes, radius, pool_k, pool_s, pool_pad):
     if logits.dim() != 4 or tuple(logits.shape) != tuple(target.shape):
         raise ValueError(f'RMILoss: logits {tuple(logits.shape)} and target {tuple(target.shape)} must be the same NCHW shape')
     return _RMI.apply(logits, target, (int(num_classes), int(radius), int(pool_k), int(pool_s), int(pool_pad)))
+
+
+# ------------------------------------------------------------------------------------------------
+# The other reference losses (csrc/seglosses.hip): CE, OHEM, Focal, NormalizedFocal, Dice, entropies
+# ------------------------------------------------------------------------------------------------
+def _bchw(x, name):
+    if x.dim() < 3:
+        raise ValueError(f'{name}: expected [B, C, ...], got {tuple(x.shape)}')
+    B, C = x.shape[:2]
+    if not 1 <= C <= 64:
+        raise ValueError(f'{name}: {C} channels (the kernels cover 1 <= C <= 64)')
+    return B, C, x[0, 0].numel()
+
+
+def _seg_ws(kind, B, C, HW, device):
+    nb = N.lib().ssseg_segloss_workspace_bytes(kind, B, C, HW)
+    return N.workspace(nb, device), nb
+
+
+def _same_shape(x, t, name):
+    if tuple(x.shape) != tuple(t.shape):
+        raise ValueError(f'{name}: input {tuple(x.shape)} and target {tuple(t.shape)} must have the same shape')
+
+
+class _CE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, t, red):
+        x, t = _c(x.float()), _c(t.float())
+        B, C, HW = _bchw(x, 'DenseCrossEntropyLossWithLogits')
+        if red == N.RED_MEAN:
+            out = torch.empty((), device=x.device, dtype=torch.float32)
+        else:
+            out = torch.empty((B,) + tuple(x.shape[2:]), device=x.device, dtype=torch.float32)
+        ws, nb = _seg_ws(N.LOSS_REDUCE, B, C, HW, x.device)
+        N.call('ssseg_ce_fwd', N.dev_ptr(x, 'input'), N.dev_ptr(t, 'target'), B, C, HW, red, N.dev_ptr(out),
+               N.dev_ptr(ws), nb, N.stream())
+        ctx.save_for_backward(x, t)
+        ctx.meta = (B, C, HW, red)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, t = ctx.saved_tensors
+        B, C, HW, red = ctx.meta
+        gx = torch.empty_like(x)
+        g = _c(g.float())
+        N.call('ssseg_ce_bwd', N.dev_ptr(x), N.dev_ptr(t), B, C, HW, red, N.dev_ptr(g), N.dev_ptr(gx), N.stream())
+        return gx, None, None
+
+
+def dense_cross_entropy(x, t, reduction='mean'):
+    """DenseCrossEntropyLossWithLogits.forward (losses.py:30-39): -(t * log_softmax(x, 1)).sum(1), mean or none."""
+    _same_shape(x, t, 'DenseCrossEntropyLossWithLogits')
+    return _CE.apply(x, t, {'mean': N.RED_MEAN, 'none': N.RED_NONE}[reduction])
+
+
+class _Ohem(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, t, thresh, min_kept):
+        x, t = _c(x.float()), _c(t.float())
+        B, C, HW = _bchw(x, 'OhemCrossEntropy')
+        out = torch.empty((), device=x.device, dtype=torch.float32)
+        # the workspace carries pred per pixel, the threshold and the kept count to the backward: a tensor of its own
+        nb = N.lib().ssseg_segloss_workspace_bytes(N.LOSS_OHEM, B, C, HW)
+        ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
+        N.call('ssseg_ohem_fwd', N.dev_ptr(x, 'logits'), N.dev_ptr(t, 'target'), B, C, HW, float(thresh),
+               int(min_kept), N.dev_ptr(out), N.dev_ptr(ws), nb, N.stream())
+        ctx.save_for_backward(x, t, ws)
+        ctx.meta = (B, C, HW)
+        ctx.mark_non_differentiable(ws)
+        ctx.set_materialize_grads(False)
+        return out, ws
+
+    @staticmethod
+    def backward(ctx, g, g_ws):
+        x, t, ws = ctx.saved_tensors
+        B, C, HW = ctx.meta
+        gx = torch.empty_like(x)
+        g = _c(g.float())
+        N.call('ssseg_ohem_bwd', N.dev_ptr(x), N.dev_ptr(t), B, C, HW, N.dev_ptr(g), N.dev_ptr(gx), N.dev_ptr(ws),
+               ws.numel(), N.stream())
+        return gx, None, None, None
+
+
+def ohem_cross_entropy(x, t, thresh, min_kept, return_state=False):
+    """OhemCrossEntropy.forward (losses.py:58-69).  return_state: also (threshold, kept count), a float64 [2] device
+    view of the forward's workspace."""
+    _same_shape(x, t, 'OhemCrossEntropy')
+    out, ws = _Ohem.apply(x, t, thresh, min_kept)
+    if return_state:
+        return out, ws[:16].view(torch.float64)
+    return out
+
+
+class _Focal(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, t, alpha, gamma):
+        x, t = _c(x.float()), _c(t.float())
+        out = torch.empty((), device=x.device, dtype=torch.float32)
+        ws, nb = _seg_ws(N.LOSS_REDUCE, 1, 1, x.numel(), x.device)
+        N.call('ssseg_focal_fwd', N.dev_ptr(x, 'inputs'), N.dev_ptr(t, 'targets'), x.numel(), alpha, gamma,
+               N.dev_ptr(out), N.dev_ptr(ws), nb, N.stream())
+        ctx.save_for_backward(x, t)
+        ctx.meta = (alpha, gamma)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, t = ctx.saved_tensors
+        gx = torch.empty_like(x)
+        g = _c(g.float())
+        N.call('ssseg_focal_bwd', N.dev_ptr(x), N.dev_ptr(t), x.numel(), *ctx.meta, N.dev_ptr(g), N.dev_ptr(gx),
+               N.stream())
+        return gx, None, None, None
+
+
+def focal_loss(x, t, alpha, gamma):
+    """FocalLoss.forward (losses.py:79-90)."""
+    _same_shape(x, t, 'FocalLoss')
+    return _Focal.apply(x, t, float(alpha), float(gamma))
+
+
+class _NFL(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, label, params, k_sum):
+        x, label = _c(x.float()), _c(label.float())
+        B, C, HW = _bchw(x, 'NormalizedFocalLossSigmoid')
+        out = torch.empty(B, device=x.device, dtype=torch.float32)
+        nb = N.lib().ssseg_segloss_workspace_bytes(N.LOSS_NFL, B, C, HW)
+        ws = torch.empty(nb, dtype=torch.uint8, device=x.device)   # mult and the denominators stay for the backward
+        N.call('ssseg_nfl_fwd', N.dev_ptr(x, 'pred'), N.dev_ptr(label, 'label'), B, C, HW, ctypes.addressof(params),
+               N.dev_ptr(out), N.dev_ptr(k_sum) if k_sum is not None else None, N.dev_ptr(ws), nb, N.stream())
+        ctx.save_for_backward(x, label, ws)
+        ctx.meta = (B, C, HW, params)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, label, ws = ctx.saved_tensors
+        B, C, HW, params = ctx.meta
+        gx = torch.empty_like(x)
+        g = _c(g.float())
+        N.call('ssseg_nfl_bwd', N.dev_ptr(x), N.dev_ptr(label), B, C, HW, ctypes.addressof(params), N.dev_ptr(g),
+               N.dev_ptr(gx), N.dev_ptr(ws), ws.numel(), N.stream())
+        return gx, None, None, None
+
+
+def normalized_focal_loss(pred, label, params, k_sum=None):
+    """NormalizedFocalLossSigmoid.forward (losses.py:115-151) -> [B]; k_sum (1 float, device) is updated in place."""
+    _same_shape(pred, label, 'NormalizedFocalLossSigmoid')
+    return _NFL.apply(pred, label, params, k_sum)
+
+
+class _DiceLogits(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, t):
+        x, t = _c(x.float()), _c(t.float())
+        B, C, HW = _bchw(x, 'DiceWithLogitsLoss')
+        out = torch.empty((), device=x.device, dtype=torch.float32)
+        nb = N.lib().ssseg_segloss_workspace_bytes(N.LOSS_DICE_LOGITS, B, C, HW)
+        ws = torch.empty(nb, dtype=torch.uint8, device=x.device)   # the per-(b,c) backward coefficients
+        N.call('ssseg_dice_logits_fwd', N.dev_ptr(x, 'input'), N.dev_ptr(t, 'target'), B, C, HW, N.dev_ptr(out),
+               N.dev_ptr(ws), nb, N.stream())
+        ctx.save_for_backward(x, t, ws)
+        ctx.meta = (B, C, HW)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, t, ws = ctx.saved_tensors
+        B, C, HW = ctx.meta
+        gx = torch.empty_like(x)
+        g = _c(g.float())
+        N.call('ssseg_dice_logits_bwd', N.dev_ptr(x), N.dev_ptr(t), B, C, HW, N.dev_ptr(g), N.dev_ptr(gx),
+               N.dev_ptr(ws), ws.numel(), N.stream())
+        return gx, None
+
+
+def dice_with_logits(x, t):
+    """DiceWithLogitsLoss.forward (losses.py:159-167)."""
+    _same_shape(x, t, 'DiceWithLogitsLoss')
+    return _DiceLogits.apply(x, t)
+
+
+class _DiceProb(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p, t, log_mode, gamma):
+        p, t = _c(p.float()), _c(t.float())
+        B = p.shape[0]
+        n = p[0].numel()
+        out = torch.empty(B, device=p.device, dtype=torch.float32)
+        nb = N.lib().ssseg_segloss_workspace_bytes(N.LOSS_DICE_PROB, B, 1, n)
+        ws = torch.empty(nb, dtype=torch.uint8, device=p.device)   # per-sample numerator and denominator
+        N.call('ssseg_dice_prob_fwd', N.dev_ptr(p, 'input'), N.dev_ptr(t, 'target'), B, n, log_mode, gamma,
+               N.dev_ptr(out), N.dev_ptr(ws), nb, N.stream())
+        ctx.save_for_backward(t, ws)
+        ctx.meta = (B, n, log_mode, gamma)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        t, ws = ctx.saved_tensors
+        B, n, log_mode, gamma = ctx.meta
+        gx = torch.empty_like(t)
+        g = _c(g.float())
+        N.call('ssseg_dice_prob_bwd', N.dev_ptr(t), B, n, log_mode, gamma, N.dev_ptr(g), N.dev_ptr(gx),
+               N.dev_ptr(ws), ws.numel(), N.stream())
+        return gx, None, None, None
+
+
+def dice_prob(p, t, log_mode=False, gamma=1.0):
+    """dice_loss / log_dice_loss (losses.py:221-236) on probabilities -> [B]."""
+    _same_shape(p, t, 'dice_loss')
+    return _DiceProb.apply(p, t, int(bool(log_mode)), float(gamma))
+
+
+class _BinaryEntropy(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        x = _c(x.float())
+        out = torch.empty((), device=x.device, dtype=torch.float32)
+        ws, nb = _seg_ws(N.LOSS_REDUCE, 1, 1, x.numel(), x.device)
+        N.call('ssseg_binary_entropy_fwd', N.dev_ptr(x, 'input'), x.numel(), N.dev_ptr(out), N.dev_ptr(ws), nb,
+               N.stream())
+        ctx.save_for_backward(x)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        gx = torch.empty_like(x)
+        g = _c(g.float())
+        N.call('ssseg_binary_entropy_bwd', N.dev_ptr(x), x.numel(), N.dev_ptr(g), N.dev_ptr(gx), N.stream())
+        return gx
+
+
+def binary_entropy(x):
+    """binary_entropy_loss (losses.py:253-257)."""
+    return _BinaryEntropy.apply(x)
+
+
+class _Entropy(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        x = _c(x.float())
+        B, C, HW = _bchw(x, 'entropy_loss')
+        out = torch.empty((), device=x.device, dtype=torch.float32)
+        ws, nb = _seg_ws(N.LOSS_REDUCE, B, C, HW, x.device)
+        N.call('ssseg_entropy_fwd', N.dev_ptr(x, 'input'), B, C, HW, N.dev_ptr(out), N.dev_ptr(ws), nb, N.stream())
+        ctx.save_for_backward(x)
+        ctx.meta = (B, C, HW)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        gx = torch.empty_like(x)
+        g = _c(g.float())
+        N.call('ssseg_entropy_bwd', N.dev_ptr(x), *ctx.meta, N.dev_ptr(g), N.dev_ptr(gx), N.stream())
+        return gx
+
+
+def entropy(x):
+    """entropy_loss (losses.py:260-264)."""
+    return _Entropy.apply(x)
+
+
+class _BCERed(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, t, red):
+        x, t = _c(x.float()), _c(t.float())
+        out = torch.empty_like(x) if red == N.RED_NONE else torch.empty((), device=x.device, dtype=torch.float32)
+        ws, nb = _seg_ws(N.LOSS_REDUCE, 1, 1, x.numel(), x.device)
+        N.call('ssseg_bce_logits_red_fwd', N.dev_ptr(x, 'x'), N.dev_ptr(t, 'target'), x.numel(), red,
+               N.dev_ptr(out), N.dev_ptr(ws), nb, N.stream())
+        ctx.save_for_backward(x, t)
+        ctx.red = red
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, t = ctx.saved_tensors
+        gx = torch.empty_like(x)
+        g = _c(g.float())
+        N.call('ssseg_bce_logits_red_bwd', N.dev_ptr(x), N.dev_ptr(t), x.numel(), ctx.red, N.dev_ptr(g),
+               N.dev_ptr(gx), N.stream())
+        return gx, None, None
+
+
+def bce_with_logits(x, t, reduction):
+    """F.binary_cross_entropy_with_logits(x, t, reduction=...) (losses.py:47); 'mean' is the hot-path kernel."""
+    if reduction == 'mean':
+        return _BCE.apply(x, t)
+    _same_shape(x, t, 'DenseBinaryCrossEntropyLossWithLogits')
+    return _BCERed.apply(x, t, {'none': N.RED_NONE, 'sum': N.RED_SUM}[reduction])
+
+
+def smooth_labels(t, alpha=0.1):
+    """smooth_labels (losses.py:267-268): t * (1 - alpha) + alpha / C (no gradient: targets)."""
+    x = _c(t.detach().float())
+    out = torch.empty_like(x)
+    N.call('ssseg_smooth_labels', N.dev_ptr(x, 'target'), N.dev_ptr(out), x.numel(), float(1 - alpha),
+           float(alpha / t.size(1)), N.stream())
+    return out
 
 
 # ------------------------------------------------------------------------------------------------
