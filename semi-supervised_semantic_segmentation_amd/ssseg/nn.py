@@ -115,48 +115,8 @@ def flush_wgrad():
             mod._ssseg_wgrad(*pair, bias_grad=False, want=(True, False))
 
 
-# ---- deferred split reductions of the weight gradients (ssseg_wgrad_defer_reduce / _flush) ---------------------------
-# opt-in (SSSEG_WGRAD_BATCH_REDUCE=1): measured neutral on the C2 step -- 519.2 / 520.1 img/s on vs 520.4 / 522.9 off,
-# A/B of two pairs in one call
-_WRED = {'on': os.environ.get('SSSEG_WGRAD_BATCH_REDUCE', '0') == '1', 'live': False, 'keep': []}
-
-
-def _wgrad_ws(nb, device):
-    """The split-slab workspace of one weight-gradient launch; inside batched_wgrad_reduce() it is kept alive until the
-    deferred reductions that read it have been launched."""
-    ws = N.workspace(nb, device)
-    if _WRED['live']:
-        _WRED['keep'].append(ws)
-    return ws
-
-
-@contextlib.contextmanager
-def batched_wgrad_reduce():
-    """Inside: the weight-gradient launches record their split-slab reductions instead of launching them; on exit ONE
-    flush launches all of them (up to 40 per launch) on the current stream -- the same per-element sums, so the same dW
-    bit for bit.  Wraps the block of weight gradients train.train_step issues after its backward passes join (66
-    reduction launches per C2 step otherwise).  Nothing inside may read a .grad those launches write."""
-    if not _WRED['on'] or _WRED['live'] or _WSTREAM['on'] or not torch.cuda.is_available():
-        yield
-        return
-    _WRED['live'] = True
-    N.call('ssseg_wgrad_defer_reduce', 1)
-    try:
-        yield
-    finally:
-        N.call('ssseg_wgrad_defer_reduce', 0)
-        _WRED['live'] = False
-        try:
-            N.call('ssseg_wgrad_reduce_flush', N.stream())
-        finally:
-            keep, _WRED['keep'] = _WRED['keep'], []
-            del keep   # (stream-ordered frees: after the flush launch that reads them)
-
-
 # ---- held weight-gradient calls: two backward passes issued on two streams, their gradient writes replayed after ------
-_HOLD = {'on': False, 'tag': None, 'calls': [], 'params': False, 'adds': [], 'streams': {},
-         # streams the replayed (merged) weight-gradient launches are spread over (SSSEG_WGRAD_BURST; 1 = this stream)
-         'burst': max(1, int(os.environ.get('SSSEG_WGRAD_BURST', '1')))}
+_HOLD = {'on': False, 'tag': None, 'calls': [], 'params': False, 'adds': []}
 
 
 @contextlib.contextmanager
@@ -222,40 +182,14 @@ def replay_held(order):
     for p, tmp in adds:   # grad += tmp (tmp = the one fp32 term the kernel would have added): bitwise the same sum
         g = _grad_of(p)
         N.call('ssseg_axpby', N.dev_ptr(g), 1.0, N.dev_ptr(tmp), 1.0, N.dev_ptr(g), g.numel(), N.stream())
-    nburst = _HOLD['burst'] if not _WRED['on'] else 1
-    streams = [cur]
-    if nburst > 1:   # the merged launches are independent (one .grad each): spread them round-robin over streams
-        pool = _HOLD['streams'].setdefault(cur.device, [])
-        while len(pool) < nburst - 1:
-            pool.append(torch.cuda.Stream(device=cur.device))
-        for sd in pool[:nburst - 1]:
-            sd.wait_stream(cur)
-            streams.append(sd)
-    first = {}
-    with batched_wgrad_reduce():
-        with defer_wgrad():
-            for tag, mod, args, kw in calls:
-                if tag == order[0]:
-                    first[id(mod)] = args
-                    mod._ssseg_wgrad(*args, **kw)
-        k = 0
+    with defer_wgrad():
         for tag, mod, args, kw in calls:
-            if tag == order[1]:
-                sd = streams[k % len(streams)]
-                k += 1
-                if sd is not cur:
-                    for t in list(args) + list(first.get(id(mod), ())):
-                        if isinstance(t, torch.Tensor) and t.is_cuda:
-                            t.record_stream(sd)
-                            vc = _vcat_of(t)
-                            if vc is not None:
-                                vc.a.record_stream(sd)
-                                vc.b.record_stream(sd)
-                with torch.cuda.stream(sd):
-                    mod._ssseg_wgrad(*args, **kw)
-        flush_wgrad()
-    for sd in streams[1:]:
-        cur.wait_stream(sd)
+            if tag == order[0]:
+                mod._ssseg_wgrad(*args, **kw)
+    for tag, mod, args, kw in calls:
+        if tag == order[1]:
+            mod._ssseg_wgrad(*args, **kw)
+    flush_wgrad()
 
 
 # ---- deferred BN parameter gradients of the differentiated eval pass ---------------------------------------------------
@@ -337,57 +271,6 @@ def flush_param_grads():
 
 def wgrad_pending():
     return sum(1 for m in _WGRAD['pending'] if '_ssseg_wg_pending' in m.__dict__)
-
-
-_WSTREAM = {'on': os.environ.get('SSSEG_WGRAD_STREAM', '0') == '1', 'live': False, 'streams': {}, 'used': False}
-
-
-@contextlib.contextmanager
-def wgrad_side_stream():
-    """Inside: every conv weight-gradient launch runs on a second HIP stream (ordered after everything issued so far
-    on the compute stream, its operands kept alive for it by record_stream), so the weight gradients -- needed only by
-    the optimizer step and the DDP buckets -- fill the compute units the input-gradient chain of the backward leaves
-    idle.  On exit the compute stream waits for the side stream.  The training step wraps its last backward in this
-    (train.train_step); outside it every launch stays on the compute stream.  Off unless SSSEG_WGRAD_STREAM=1: on the
-    C2 step it measured 440.8 vs 443.9 img/s (A/B in one call; the teacher-pass overlap alone: 452.9)."""
-    if not _WSTREAM['on'] or _WSTREAM['live'] or not torch.cuda.is_available():
-        yield
-        return
-    _WSTREAM['live'] = True
-    try:
-        yield
-    finally:
-        _WSTREAM['live'] = False
-        join_wgrad_stream()
-
-
-def join_wgrad_stream():
-    if _WSTREAM['used']:
-        _WSTREAM['used'] = False
-        torch.cuda.current_stream().wait_stream(_WSTREAM['streams'][torch.cuda.current_device()])
-
-
-@contextlib.contextmanager
-def _on_wgrad_stream(*tensors):
-    """the launches inside go to the weight-gradient stream when wgrad_side_stream() is live"""
-    if not _WSTREAM['live']:
-        yield
-        return
-    dev = torch.cuda.current_device()
-    s = _WSTREAM['streams'].get(dev)
-    if s is None:
-        s = _WSTREAM['streams'][dev] = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    for t in tensors:
-        if isinstance(t, torch.Tensor) and t.is_cuda:
-            t.record_stream(s)
-            vc = _vcat_of(t)
-            if vc is not None:
-                vc.a.record_stream(s)
-                vc.b.record_stream(s)
-    _WSTREAM['used'] = True
-    with torch.cuda.stream(s):
-        yield
 
 
 def set_fused_bn_stats(flag):
@@ -1146,9 +1029,7 @@ class Conv2d(nn.Conv2d, _ConvBase):
             return
         if self._wg_defer(x, gy):
             return
-        pend = self._wg_take(x, gy)
-        with _on_wgrad_stream(x, gy, *(pend or ())):
-            self._wgrad_launch(x, gy, pend)
+        self._wgrad_launch(x, gy, self._wg_take(x, gy))
 
     def _wgrad_launch(self, x, gy, pend):
         n, _, H, W = x.shape
@@ -1156,7 +1037,7 @@ class Conv2d(nn.Conv2d, _ConvBase):
         if pend is None:
             d = self._fwd_desc(n, H, W)
             nb = N.lib().ssseg_conv_wgrad_workspace_bytes(ctypes_ref(d), N.dt_code(x))
-            ws = _wgrad_ws(nb, x.device)
+            ws = N.workspace(nb, x.device)
             vc = _vcat_of(x)
             with _Timed(_conv_flops(n, d.OH, d.OW, self.out_channels, self.in_channels, R, S), 'wgrad',
                         _tag(self, n, H, W)):
@@ -1174,7 +1055,7 @@ class Conv2d(nn.Conv2d, _ConvBase):
             n1 = x1.shape[0]
             d = self._fwd_desc(n1, H, W)
             nb = N.lib().ssseg_conv_wgrad2_workspace_bytes(ctypes_ref(d), n, N.dt_code(x))
-            ws = _wgrad_ws(nb, x.device)
+            ws = N.workspace(nb, x.device)
             v1, v2 = _vcat_of(x1), _vcat_of(x)
             with _Timed(_conv_flops(n1 + n, d.OH, d.OW, self.out_channels, self.in_channels, R, S), 'wgrad',
                         _tag(self, n1 + n, H, W)):
@@ -1410,9 +1291,7 @@ class ConvTranspose2d(nn.ConvTranspose2d, _ConvBase):
         if ww:
             if self._wg_defer(x, gy):
                 return
-            pend = self._wg_take(x, gy)
-            with _on_wgrad_stream(x, gy, *(pend or ())):
-                self._wgrad_launch(x, gy, pend, want)
+            self._wgrad_launch(x, gy, self._wg_take(x, gy), want)
             return
         wb = self.bias is not None and (self.bias.requires_grad if want is None else want[1])
         _ready(*[p for p, on in ((self.bias, wb),) if on])
@@ -1428,7 +1307,7 @@ class ConvTranspose2d(nn.ConvTranspose2d, _ConvBase):
                   py=-ph, px=-pw, outH=H, outW=W, osy=1, osx=1, ooy=0, oox=0, ldy=cin, ldw=R * S * cout)
         if pend is None:
             nb = N.lib().ssseg_conv_wgrad_workspace_bytes(ctypes_ref(d), N.dt_code(x))
-            ws = _wgrad_ws(nb, x.device)
+            ws = N.workspace(nb, x.device)
             with _Timed(_conv_flops(n, H, W, self.out_channels, self.in_channels, R, S), 'wgrad',
                         _tag(self, n, H, W)):
                 N.call('ssseg_conv_wgrad', N.dev_ptr(gy), N.dev_ptr(x), N.dev_ptr(_grad_of(self.weight)),
@@ -1437,7 +1316,7 @@ class ConvTranspose2d(nn.ConvTranspose2d, _ConvBase):
         else:   # the deferred pass and this one: one launch over both pixel sets (operands in (gy, x) order)
             x1, gy1 = pend
             nb = N.lib().ssseg_conv_wgrad2_workspace_bytes(ctypes_ref(d), n, N.dt_code(x))
-            ws = _wgrad_ws(nb, x.device)
+            ws = N.workspace(nb, x.device)
             with _Timed(_conv_flops(n1 + n, H, W, self.out_channels, self.in_channels, R, S), 'wgrad',
                         _tag(self, n1 + n, H, W)):
                 N.call('ssseg_conv_wgrad2', N.dev_ptr(gy1), N.dev_ptr(x1), N.dev_ptr(gy), N.dev_ptr(x), n,

@@ -118,8 +118,7 @@ def _scaled(loss, optimizer):
 _OVERLAP = {'teacher': os.environ.get('SSSEG_OVERLAP_TEACHER', '1') != '0', 'streams': {}, 'steps': 0,
             'serial_steps': 2, 'seen': {},
             'consistency': os.environ.get('SSSEG_OVERLAP_CONSISTENCY', '1') != '0',
-            'consistency_bwd': os.environ.get('SSSEG_OVERLAP_CONSISTENCY_BWD', '1') != '0',
-            'merge_wgrad': os.environ.get('SSSEG_MERGE_WGRAD', '1') != '0'}
+            'consistency_bwd': os.environ.get('SSSEG_OVERLAP_CONSISTENCY_BWD', '1') != '0'}
 
 
 def _step_key(model, ema_model, image, unsup_a):
@@ -185,10 +184,9 @@ def train_step(model, ema_model, optimizer, image, mask, unsup_a, unsup_b, epoch
     and runs concurrently with the supervised backward (and, in C5, the discriminator step).  The consistency forward
     (train.py:87-112) reads the same weights and statistics, so it follows the teacher on the side stream; its
     backward runs after the supervised backward's gradient writes (autograd runs it on the side stream, its forward's:
-    explicit waits on both sides).  The consistency backward can put its (merged) weight gradients on a side stream too
-    (ssseg.nn.wgrad_side_stream; off by default, measured neutral).  Measured (A/B in one call): C2 443.9 img/s serial,
-    452.9 with the teacher overlap (round 4); 499.7 / 501.9 -> 512.9 / 514.8 with the consistency forward on the side
-    stream too; C5 25.5 -> 21.9 ms (the overlap was off for the adversarial config before)."""
+    explicit waits on both sides).  Measured (A/B in one call): C2 443.9 img/s serial, 452.9 with the teacher overlap
+    (round 4); 499.7 / 501.9 -> 512.9 / 514.8 with the consistency forward on the side stream too; C5 25.5 -> 21.9 ms
+    (the overlap was off for the adversarial config before)."""
     tc = config['train']
     ddp = model if isinstance(model, _DDP) else None
     semi = tc['use_semi_supervised']
@@ -237,12 +235,9 @@ def train_step(model, ema_model, optimizer, image, mask, unsup_a, unsup_b, epoch
         if ddp is not None and not semi:
             ddp.arm()
         # with a consistency backward to follow, each conv's supervised weight gradient is merged into that pass's
-        # (one launch over both batches' pixels; ssseg.nn.defer_wgrad) -- the .grad sum is the same
-        # (merge_wgrad off: the supervised weight gradients are launched in its backward -- written into .grad while
-        # the side stream still runs the teacher and consistency passes -- and the consistency pass's add to them)
-        merge = _OVERLAP['merge_wgrad']
-        with (snn.hold_wgrad('sup') if side_bwd and merge else snn.defer_wgrad() if semi and merge
-              else contextlib.nullcontext()):
+        # (one launch over both batches' pixels; ssseg.nn.defer_wgrad) -- the .grad sum is the same; with both backward
+        # passes in flight it is held instead (ssseg.nn.hold_wgrad) and replay_held() does the merge after the join
+        with snn.hold_wgrad('sup') if side_bwd else snn.defer_wgrad() if semi else contextlib.nullcontext():
             vbm = tc['virtual_batch_size_multiplier']
             ops.backward(_scaled(ops.scale(sup_loss, 1.0 / vbm) if vbm != 1 else sup_loss, optimizer))
         del pred_maps, features
@@ -262,27 +257,26 @@ def train_step(model, ema_model, optimizer, image, mask, unsup_a, unsup_b, epoch
             semi_rest = False
         else:
             semi_rest = semi
-    with snn.wgrad_side_stream():
-        if semi_rest:
-            if overlap:
-                torch.cuda.current_stream().wait_stream(_side_stream(image.device))
-            else:
-                targets = _teacher_targets(ema_model, unsup_a, unsup_b, tc)
-            side_fwd = cons is not None
-            unsup_loss, cm_mean = cons if side_fwd else _consistency_forward(model, targets, tc, epoch)
-            del targets, cons
-            if ddp is not None:
-                ddp.arm()
-            with snn.defer_param_grads():   # the eval BNs' parameter gradients: one batched reduction at the end
-                if side_fwd:
-                    # autograd runs each backward node on its forward's stream: the consistency backward runs on the
-                    # side stream, after the supervised backward's gradient writes (main) and before what follows
-                    side = _side_stream(image.device)
-                    side.wait_stream(torch.cuda.current_stream())
-                ops.backward(_scaled(unsup_loss, optimizer))
-                if side_fwd:
-                    torch.cuda.current_stream().wait_stream(side)
-        snn.flush_wgrad()
+    if semi_rest:
+        if overlap:
+            torch.cuda.current_stream().wait_stream(_side_stream(image.device))
+        else:
+            targets = _teacher_targets(ema_model, unsup_a, unsup_b, tc)
+        side_fwd = cons is not None
+        unsup_loss, cm_mean = cons if side_fwd else _consistency_forward(model, targets, tc, epoch)
+        del targets, cons
+        if ddp is not None:
+            ddp.arm()
+        with snn.defer_param_grads():   # the eval BNs' parameter gradients: one batched reduction at the end
+            if side_fwd:
+                # autograd runs each backward node on its forward's stream: the consistency backward runs on the
+                # side stream, after the supervised backward's gradient writes (main) and before what follows
+                side = _side_stream(image.device)
+                side.wait_stream(torch.cuda.current_stream())
+            ops.backward(_scaled(unsup_loss, optimizer))
+            if side_fwd:
+                torch.cuda.current_stream().wait_stream(side)
+    snn.flush_wgrad()
     if ddp is not None:
         ddp.finish()
     if step % tc['virtual_batch_size_multiplier'] == 0 and step != 0:

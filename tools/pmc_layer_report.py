@@ -1,5 +1,6 @@
-"""Per-config PMC anatomy of one conv layer from the three rocprofv3 --pmc passes of tools/r6_pmc_layers.sh (each pass ran
-tools/one_layer.py with the autotuner on, so every candidate config of the geometry was dispatched 6x): per config,
+"""Per-config PMC anatomy of one conv layer from three rocprofv3 --pmc passes over it (wave-cycle anatomy; texture path /
+L2 latency; L2 hits / LDS conflicts -- directories <prefix>_p1, _p2, _p3; each pass ran tools/one_layer.py with the
+autotuner on, so every candidate config of the geometry was dispatched 6x): per config,
 cycles per dispatch, MFMA utilisation, wave-cycle shares (waiting / issue-stalled / issuing), texture-path busy, L2
 request latency and hit rate, LDS bank conflicts.
 
