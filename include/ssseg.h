@@ -429,6 +429,19 @@ int ssseg_conv_igemm_epi(const void* x, const void* w, void* y, const ssseg_conv
 int ssseg_conv_igemm_epi_actmask(const void* x, const void* w, void* y, const ssseg_conv_desc* desc_host, int dt,
                                  int dt_out, const ssseg_conv_epilogue* epi, int act, float slope, void* ws,
                                  size_t ws_bytes, ssseg_stream_t stream);
+/* ssseg_conv_igemm_epi for the input gradient of a conv whose input z is the ReLU output of a residual join that only
+ * this conv and the next join's shortcut read (a ResNet Bottleneck without downsample: z = relu(bn3(..) + z_prev) feeds
+ * the next block's conv1 and its shortcut).  epi->residual is the pending shortcut gradient (an addend, as in
+ * ssseg_conv_igemm_epi), mask is z itself (dtype dt_out, pixel stride ldm >= K):
+ *   y[m][n] = mask[pixel(m)][n] > 0 ? stored(acc[m][n] + residual[pixel(m)][n]) : 0
+ * i.e. the complete gradient of z with the join's ReLU backward applied -- bit for bit what the residual epilogue
+ * followed by ssseg_act_bwd stores.  It is both the shortcut gradient and the dy of the join's BatchNorm, whose
+ * backward then needs neither the residual (to rebuild the mask) nor a separate shortcut-gradient tensor.  epi carries
+ * no scale / shift / activation / aux / stats.  SSSEG_EUNSUPPORTED where no kernel takes the launch (an empty tap set,
+ * mixed dtypes): run the plain epilogue. */
+int ssseg_conv_igemm_epi_join(const void* x, const void* w, void* y, const ssseg_conv_desc* desc_host, int dt,
+                              int dt_out, const ssseg_conv_epilogue* epi, const void* mask, int64_t ldm, void* ws,
+                              size_t ws_bytes, ssseg_stream_t stream);
 /* Virtual channel concat of a conv input (reference models/unet.py:44-45, torch.cat((x, skip), 1) feeding
  * UpBlock.conv3_0): input channels [0, c1) are read from x (pixel stride desc.ldx) and [c1, desc.C) from x2
  * (pixel stride ldx2, channel 0 of x2 = input channel c1); same N x H x W.  c1 and C - c1 are multiples of 64

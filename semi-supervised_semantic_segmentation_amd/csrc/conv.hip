@@ -396,7 +396,8 @@ int dispatch_igemm(const void* x, const void* w, void* y, const ConvGeom& g, con
       if (v == 0) {
         const unsigned long long key =
             geom_key(g, (int)sizeof(TO) * 8 + (ep.stats ? 4 : 0) + (ep.res ? 2 : 0) + (ep.scale ? 1 : 0) + 16 * S +
-                        256 * nph + (x2 ? 4096 * (g.c1b + 1) : 0) + (ep.y2 ? (1 << 24) : 0) + (ep.rmask ? (1 << 25) : 0) + (ep.gstat ? (1 << 26) : 0));
+                        256 * nph + (x2 ? 4096 * (g.c1b + 1) : 0) + (ep.y2 ? (1 << 24) : 0) + (ep.rmask ? (1 << 25) : 0) + (ep.gstat ? (1 << 26) : 0) +
+                        (ep.zmask ? (1 << 27) : 0));
         std::lock_guard<std::mutex> lk(g_variant_mu);
         auto it = g_variant.find(key);
         if (it != g_variant.end()) {
@@ -425,6 +426,13 @@ int dispatch_igemm(const void* x, const void* w, void* y, const ConvGeom& g, con
       // a forced config without a general-k instantiation (128/256-wide n-tiles, C % 64 != 0): register-staged
       if (r == -1 && g_knobs[4] != 0 && !x2 && g.C % 64 && g.C <= g.ldx)
         return run_variant<T, TO>(0, x, w, y, g, ep, 0, 0, s, nullptr, ph);
+      // a forced, cached or imported variant without the residual-join epilogue (the 256 x 256 tile, the halo and
+      // pointwise kernels): the heuristic's, whose every choice has it
+      if (r == -1 && ep.zmask) {
+        int hv = heuristic_variant(g);
+        if ((g.C > g.ldx || S > 1) && (hv == 0 || hv >= 24)) hv = 14;
+        return run_variant<T, TO>(hv, x, w, y, g, ep, (unsigned)xb, (unsigned)wb, s, S > 1 ? wsv : nullptr, ph);
+      }
       if (r == -1 && g_knobs[4] >= 24 && g_knobs[4] <= 28) {   // a forced halo / pointwise kernel does not apply: the heuristic's
         const int hv = x2 && heuristic_variant(g) == 0 ? 5 : heuristic_variant(g);
         return run_variant<T, TO>(hv, x, w, y, g, ep, (unsigned)xb, (unsigned)wb, s, nullptr, ph, x2, (unsigned)x2b);
@@ -507,7 +515,7 @@ extern "C" size_t ssseg_conv_igemm_workspace_bytes(const ssseg_conv_desc* d, int
 static int conv_igemm_epi(const void* x, const void* x2, int64_t c1, int64_t ldx2, const void* w, void* y,
                           const ssseg_conv_desc* d, int dt, int dt_out, const ssseg_conv_epilogue* epi, void* ws,
                           size_t ws_bytes, ssseg_stream_t stream, const ssseg_vcat* ysplit = nullptr,
-                          int mask_act = 0, float mask_slope = 0.f) {
+                          int mask_act = 0, float mask_slope = 0.f, const void* jmask = nullptr, int64_t ldm = 0) {
   ConvGeom g;
   if (!make_geom(d, g) || !y) return SSSEG_EINVAL;
   if (!geom_ok(g, dt)) return SSSEG_EINVAL;
@@ -545,6 +553,16 @@ static int conv_igemm_epi(const void* x, const void* x2, int64_t c1, int64_t ldx
     ef.rmask = eb.rmask = eh.rmask = mask_act;
     ef.rslope = eb.rslope = eh.rslope = mask_slope;
     ef.gstat = eb.gstat = eh.gstat = gst ? 1 : 0;
+  }
+  if (jmask) {   // residual join: the residual is added, then the value is cut where jmask (the input's ReLU output) <= 0
+    if (ysplit || x2 || mask_act || !e.residual || e.aux || e.relu || e.shift || e.scale || e.stats || ldm < g.K ||
+        ldm > 0x7fffffff)
+      return SSSEG_EINVAL;
+    if (dt != dt_out || g.KK == 0) return SSSEG_EUNSUPPORTED;
+    ef.zmask = (const float*)jmask;
+    eb.zmask = (const bf16_t*)jmask;
+    eh.zmask = (const f16_t*)jmask;
+    ef.ldz = eb.ldz = eh.ldz = (int)ldm;
   }
   if (ysplit) {   // split output: channels [c1, K) to ysplit->x2 (pixel stride ldx2); 16-bit, plain epilogue
     const int64_t oc1 = ysplit->c1, ld2 = ysplit->ldx2;
@@ -623,6 +641,13 @@ extern "C" int ssseg_conv_igemm_epi_actmask(const void* x, const void* w, void* 
                                             size_t ws_bytes, ssseg_stream_t stream) {
   if (act != SSSEG_ACT_RELU && act != SSSEG_ACT_LEAKY) return SSSEG_EINVAL;
   return conv_igemm_epi(x, nullptr, 0, 0, w, y, d, dt, dt_out, epi, ws, ws_bytes, stream, nullptr, act, slope);
+}
+
+extern "C" int ssseg_conv_igemm_epi_join(const void* x, const void* w, void* y, const ssseg_conv_desc* d, int dt,
+                                         int dt_out, const ssseg_conv_epilogue* epi, const void* mask, int64_t ldm,
+                                         void* ws, size_t ws_bytes, ssseg_stream_t stream) {
+  if (!mask || !epi) return SSSEG_EINVAL;
+  return conv_igemm_epi(x, nullptr, 0, 0, w, y, d, dt, dt_out, epi, ws, ws_bytes, stream, nullptr, 0, 0.f, mask, ldm);
 }
 
 extern "C" int ssseg_conv_igemm_epi_vcat(const void* x, const ssseg_vcat* vc, const void* w, void* y,

@@ -215,6 +215,7 @@ static void launch_hconv3_w(int tw, const void* x, const void* w, void* y, const
 template <typename TO>
 int launch_hconv3(const void* x, const void* w, void* y, const ConvGeom& g, const Epi<TO>& ep, unsigned xb,
                   unsigned wb, hipStream_t s, float* ws, const PhaseTab* ph, const void* x2, unsigned x2b, int mode) {
+  if (ep.zmask) return -1;   // (no residual-join epilogue here)
   if (!hconv3_ok(g, ph, ws) || (x2 && (g.ldx2 % 8 || g.c1b < 1 || g.c1b >= g.C / 64))) return -1;
   if (mode == 1 && g_knobs[15] < 0) return -1;   // knob 15 = -1: no variant 28 (A/B)
   const int tw = hconv3_tw(g);

@@ -125,7 +125,7 @@ bool hconv3s_ok(const ConvGeom& g, const PhaseTab* ph, const float* ws) {
 template <typename TO>
 int launch_hconv3s(const void* x, const void* w, void* y, const ConvGeom& g, const Epi<TO>& ep, unsigned xb,
                    hipStream_t s, float* ws, const PhaseTab* ph, const void* x2) {
-  if (x2 || !hconv3s_ok(g, ph, ws)) return -1;
+  if (x2 || ep.zmask || !hconv3s_ok(g, ph, ws)) return -1;
   const long long tiles = (long long)g.N * (g.H / 4) * (g.W / 64);
   if (tiles > 0x7fffffffLL) return -1;
   // two resident blocks per CU (73.7 KB of LDS each): a grid of 2 x 256 covers the chip once, every block then

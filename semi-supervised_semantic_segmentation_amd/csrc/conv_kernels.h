@@ -192,6 +192,11 @@ struct Epi {
   // scale, rounded to TO -- the two sums a BatchNorm backward reduces (res = its output y, from which x_hat follows
   // wherever m != 0); the stored value is scale * m
   int gstat = 0;
+  // join (the JOIN instantiations only): res IS added (the pending shortcut gradient of the conv's input) and the stored
+  // value is then cut where zmask (the conv's own forward input, a ReLU output; pixel stride ldz) is not positive:
+  // y = zmask > 0 ? stored(acc + res) : 0 -- the complete masked gradient of a residual join's output
+  const TO* zmask = nullptr;
+  int ldz = 0;
   int sdbg = 0;  // experiment switch for the fused statistics (knob 12): 1 no sums, 2 no tile_stats, 4 no row write,
                   // 8 no cross-lane shuffles
 };
@@ -292,7 +297,7 @@ template <> struct Load4<bf16_t> {
 // The per-channel affine of a fragment column is loaded once, and every residual of the column is loaded
 // before the first store (the stores may alias the residual as far as the compiler knows, so it could not
 // batch those loads itself): one HBM round trip per column instead of one per pixel.
-template <typename TO, int FM, int FN, bool ST = false>
+template <typename TO, int FM, int FN, bool ST = false, bool JOIN = false>
 __device__ __forceinline__ void store_tile(const f32x4 (&acc)[FN][FM], long long mb, int nb, int lane,
                                            const ConvGeom& g, TO* __restrict__ y, const Epi<TO>& ep,
                                            double (*st1)[4] = nullptr, double (*st2)[4] = nullptr) {
@@ -331,6 +336,23 @@ __device__ __forceinline__ void store_tile(const f32x4 (&acc)[FN][FM], long long
             if (n + e < g.K) r[j][e] = io<TO>::ld(rp, e);
       }
     }
+    unsigned zm[JOIN ? FM : 1];   // JOIN: bit e = (zmask of channel n + e > 0), fragment row j
+    if constexpr (JOIN) {
+#pragma unroll
+      for (int j = 0; j < FM; ++j) {
+        float z[4] = {0.f, 0.f, 0.f, 0.f};
+        if (op[j] >= 0) {
+          const TO* zp = ep.zmask + op[j] * ep.ldz + n;
+          if (full && (ep.ldz & 3) == 0)
+            Load4<TO>::ld(zp, z);
+          else
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+              if (n + e < g.K) z[e] = io<TO>::ld(zp, e);
+        }
+        zm[j] = (z[0] > 0.f ? 1u : 0u) | (z[1] > 0.f ? 2u : 0u) | (z[2] > 0.f ? 4u : 0u) | (z[3] > 0.f ? 8u : 0u);
+      }
+    }
 #pragma unroll
     for (int j = 0; j < FM; ++j) {
       if (op[j] < 0) continue;
@@ -352,6 +374,7 @@ __device__ __forceinline__ void store_tile(const f32x4 (&acc)[FN][FM], long long
         if (!ep.rmask) a += r[j][e];
         a = act_fwd(a, ep.relu, ep.slope);
         if (ep.rmask && n < ep.oc1 && !(r[j][e] > 0.f)) a = ep.rmask == SSSEG_ACT_LEAKY ? a * ep.rslope : 0.f;
+        if constexpr (JOIN) a = (zm[j] >> e) & 1u ? a : 0.f;
         v[e] = a;
         if constexpr (ST) {   // compile-time: the statistics arrays stay in registers
           if (n + e < g.K) {
@@ -446,7 +469,8 @@ struct Tile2D {
   int lw = 6;   // log2 of the tile width (64 columns; 32 / 16 on the 32^2 / 16^2 maps)
 };
 
-template <typename TO, int BM, int BN, int FM, int FN, int NT, bool STATS, int NPRE = 1, bool T2D = false>
+template <typename TO, int BM, int BN, int FM, int FN, int NT, bool STATS, int NPRE = 1, bool T2D = false,
+          bool JOIN = false>
 __device__ __forceinline__ void store_tile_lds(const f32x4 (&acc)[FN][FM], char* smem, long long m0, int n0, int wmo,
                                                int wno, int lane, const ConvGeom& g, TO* __restrict__ y,
                                                const Epi<TO>& ep, PreRes<NPRE> pre = PreRes<NPRE>{{}, false},
@@ -546,27 +570,42 @@ __device__ __forceinline__ void store_tile_lds(const f32x4 (&acc)[FN][FM], char*
 #pragma unroll
   for (int e = 0; e < (STATS ? 8 : 1); ++e) s1[e] = s2[e] = (SA)0;
   if (n < g.K) {
-    const bool vec = (g.ldy & 7) == 0 && (!ep.res || (ep.ldr & 7) == 0);
+    const bool vec = (g.ldy & 7) == 0 && (!ep.res || (ep.ldr & 7) == 0) && (!JOIN || (ep.ldz & 7) == 0);
     const bool full = vec && n + 7 < g.K;
     // this thread's 8 channels are the same in every pass: the affine is loaded once, and all residual
     // rows are in flight before the first store
-    float sc[8], sh[8];
-    if (full && ep.scale && ((reinterpret_cast<uintptr_t>(ep.scale) & 15) == 0)) {   // two 16-byte loads
-      const float4 a = *(const float4*)(ep.scale + n), b = *(const float4*)(ep.scale + n + 4);
-      sc[0] = a.x; sc[1] = a.y; sc[2] = a.z; sc[3] = a.w; sc[4] = b.x; sc[5] = b.y; sc[6] = b.z; sc[7] = b.w;
-    } else {
+    float sc[JOIN ? 1 : 8], sh[JOIN ? 1 : 8];   // (the join form has no affine)
+    if constexpr (!JOIN) {
+      if (full && ep.scale && ((reinterpret_cast<uintptr_t>(ep.scale) & 15) == 0)) {   // two 16-byte loads
+        const float4 a = *(const float4*)(ep.scale + n), b = *(const float4*)(ep.scale + n + 4);
+        sc[0] = a.x; sc[1] = a.y; sc[2] = a.z; sc[3] = a.w; sc[4] = b.x; sc[5] = b.y; sc[6] = b.z; sc[7] = b.w;
+      } else {
 #pragma unroll
-      for (int e = 0; e < 8; ++e) sc[e] = (ep.scale && n + e < g.K) ? ep.scale[n + e] : 1.f;
-    }
-    if (full && ep.shift && ((reinterpret_cast<uintptr_t>(ep.shift) & 15) == 0)) {
-      const float4 a = *(const float4*)(ep.shift + n), b = *(const float4*)(ep.shift + n + 4);
-      sh[0] = a.x; sh[1] = a.y; sh[2] = a.z; sh[3] = a.w; sh[4] = b.x; sh[5] = b.y; sh[6] = b.z; sh[7] = b.w;
-    } else {
+        for (int e = 0; e < 8; ++e) sc[e] = (ep.scale && n + e < g.K) ? ep.scale[n + e] : 1.f;
+      }
+      if (full && ep.shift && ((reinterpret_cast<uintptr_t>(ep.shift) & 15) == 0)) {
+        const float4 a = *(const float4*)(ep.shift + n), b = *(const float4*)(ep.shift + n + 4);
+        sh[0] = a.x; sh[1] = a.y; sh[2] = a.z; sh[3] = a.w; sh[4] = b.x; sh[5] = b.y; sh[6] = b.z; sh[7] = b.w;
+      } else {
 #pragma unroll
-      for (int e = 0; e < 8; ++e) sh[e] = (ep.shift && n + e < g.K) ? ep.shift[n + e] : 0.f;
+        for (int e = 0; e < 8; ++e) sh[e] = (ep.shift && n + e < g.K) ? ep.shift[n + e] : 0.f;
+      }
     }
     long long op[NP];
-    float r[NP][8];
+    float r[JOIN ? 1 : NP][8];
+    // JOIN: what a pass reads stays packed until its turn (4 + 1 registers per pass instead of 8 + 8): the pending
+    // gradient's 8 raw values, bit e = (zmask of channel n + e > 0)
+    u32x4 rq[JOIN ? NP : 1];
+    unsigned zm[JOIN ? NP : 1];
+    auto ld8raw = [&](const TO* q) {   // 8 channels from q as stored (zeros past K)
+      static_assert(!JOIN || sizeof(TO) == 2, "LDS-staged join epilogue: 16-bit activations");
+      if (full) return *(const u32x4*)q;
+      unsigned h[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) h[e] = n + e < g.K ? (unsigned)*((const unsigned short*)q + e) : 0u;
+      return u32x4{h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16)};
+    };
+    (void)ld8raw;
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
       const int row = r0 + p * RPP;
@@ -580,24 +619,37 @@ __device__ __forceinline__ void store_tile_lds(const f32x4 (&acc)[FN][FM], char*
           op[p] = out_pixel(g, (int)m);   // M < 2^31 (geom_ok)
         }
       }
+      if constexpr (JOIN) {
+        rq[p] = u32x4{0u, 0u, 0u, 0u};
+        zm[p] = 0u;
+        if (op[p] >= 0) {
+          rq[p] = pre.on ? pre.v[p < NPRE ? p : 0] : ld8raw(ep.res + op[p] * ep.ldr + n);
+          const u32x4 zq = ld8raw(ep.zmask + op[p] * ep.ldz + n);
+          float z[8];
+          Chunk<TO, 8>::cvt(make_uint4(zq.x, zq.y, zq.z, zq.w), z);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) r[p][e] = 0.f;
+          for (int e = 0; e < 8; ++e) zm[p] |= z[e] > 0.f ? 1u << e : 0u;
+        }
+        continue;
+      }
+#pragma unroll
+      for (int e = 0; e < 8; ++e) r[JOIN ? 0 : p][e] = 0.f;
       if (ep.res && op[p] >= 0 && n < ep.oc1) {
         if (full) {
           if constexpr (sizeof(TO) == 2) {
             if (pre.on) {
               const u32x4 q = pre.v[p < NPRE ? p : 0];
-              Chunk<TO, 8>::cvt(make_uint4(q.x, q.y, q.z, q.w), r[p]);
+              Chunk<TO, 8>::cvt(make_uint4(q.x, q.y, q.z, q.w), r[JOIN ? 0 : p]);
             } else {
-              Out8<TO>::ld(ep.res + op[p] * ep.ldr + n, r[p]);
+              Out8<TO>::ld(ep.res + op[p] * ep.ldr + n, r[JOIN ? 0 : p]);
             }
           } else {
-            Out8<TO>::ld(ep.res + op[p] * ep.ldr + n, r[p]);
+            Out8<TO>::ld(ep.res + op[p] * ep.ldr + n, r[JOIN ? 0 : p]);
           }
         } else
 #pragma unroll
           for (int e = 0; e < 8; ++e)   // fixed trip count: r stays in registers (a runtime bound spills it)
-            if (n + e < g.K) r[p][e] = io<TO>::ld(ep.res, op[p] * ep.ldr + n + e);
+            if (n + e < g.K) r[JOIN ? 0 : p][e] = io<TO>::ld(ep.res, op[p] * ep.ldr + n + e);
       }
     }
 #pragma unroll
@@ -608,7 +660,12 @@ __device__ __forceinline__ void store_tile_lds(const f32x4 (&acc)[FN][FM], char*
       const float4 a0 = *(const float4*)a, a1 = *(const float4*)(a + 4);
       const float raw[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
       // affine + residual, then ONE uniform activation switch per chunk (not one per value)
-      if (ep.rmask) {   // split output with the first part's ReLU backward (no residual add)
+      if constexpr (JOIN) {   // acc + pending gradient, cut by the join's ReLU (no affine, no activation)
+        float rf[8];
+        Chunk<TO, 8>::cvt(make_uint4(rq[p].x, rq[p].y, rq[p].z, rq[p].w), rf);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = (zm[p] >> e) & 1u ? raw[e] + rf[e] : 0.f;
+      } else if (ep.rmask) {   // split output with the first part's ReLU backward (no residual add)
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = raw[e] * sc[e] + sh[e];
         act8(v, ep.relu, ep.slope);
@@ -734,7 +791,8 @@ extern int g_knobs[17];   // runtime variant switches (ssseg_set_knob), defined 
 
 // STATS: the epilogue also writes the fused BatchNorm statistics partials (a separate instantiation: the fp64
 // sums raise the register count, which must not cost the launches that do not need them)
-template <typename T, typename TO, int BM, int BN, int WM, int WN, bool DEEP, bool STATS = false>
+// JOIN: the residual-join input-gradient epilogue (Epi::zmask), its own instantiation for the same reason
+template <typename T, typename TO, int BM, int BN, int WM, int WN, bool DEEP, bool STATS = false, bool JOIN = false>
 __global__ void __launch_bounds__(256, DEEP ? 2 : 1) igemm_kernel(const T* __restrict__ x, const T* __restrict__ w,
                                                                   TO* __restrict__ y, ConvGeom g, Epi<TO> ep,
                                                                   int splits, float* __restrict__ ws) {
@@ -923,7 +981,7 @@ __global__ void __launch_bounds__(256, DEEP ? 2 : 1) igemm_kernel(const T* __res
     frag_stats<FN, BN, 4>(st1, st2, wn * WTN, smem, m0 / BM, n0, ep.stats, ep.sld);
     return;
   }
-  store_tile<TO, FM, FN>(acc, m0 + wm * WTM, n0 + wn * WTN, lane, g, y, ep);
+  store_tile<TO, FM, FN, false, JOIN>(acc, m0 + wm * WTM, n0 + wn * WTN, lane, g, y, ep);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1058,7 +1116,7 @@ __device__ __forceinline__ bool dsplit_combine(f32x4 (&acc)[FN][FM], float* ws, 
       ((BM) == 256 && (BN) == 64 && (NW) == 8 && (NS) == 2))                                                     \
        ? 4                                                                                                       \
        : ((SSSEG_GLDS_OCC_MODE >= 2 && (BM) == 128 && (BN) == 64 && (NW) == 8 && (NS) == 2) ? 6 : 1))
-template <typename TO, int BM, int BN, int WM, int WN, int NW, int NS, bool STATS, int KM = 0>
+template <typename TO, int BM, int BN, int WM, int WN, int NW, int NS, bool STATS, int KM = 0, bool JOIN = false>
 __global__ void __launch_bounds__(NW * 64, GLDS_OCC(BM, BN, NW, NS)) igemm_glds_kernel(const TO* __restrict__ x,
                                                                 const TO* __restrict__ w, TO* __restrict__ y,
                                                                 ConvGeom g, Epi<TO> ep, unsigned xbytes,
@@ -1315,8 +1373,8 @@ __global__ void __launch_bounds__(NW * 64, GLDS_OCC(BM, BN, NW, NS)) igemm_glds_
     // the LDS-staged epilogue whenever the staged tile fits the ring (the register epilogue is not even compiled
     // then: as dead code it cost the statistics instantiations a scratch frame)
     (void)g_epi_lds;
-    store_tile_lds<TO, BM, BN, FM, FN, NW * 64, STATS, PRE ? EP_NP : 1>(acc, smem, m0, n0, wm * WTM, wn * WTN, lane,
-                                                                        g, y, ep, pre);
+    store_tile_lds<TO, BM, BN, FM, FN, NW * 64, STATS, PRE ? EP_NP : 1, false, JOIN>(acc, smem, m0, n0, wm * WTM,
+                                                                                     wn * WTN, lane, g, y, ep, pre);
   } else if constexpr (STATS) {
     double st1[FN][4], st2[FN][4];
 #pragma unroll
@@ -1326,7 +1384,7 @@ __global__ void __launch_bounds__(NW * 64, GLDS_OCC(BM, BN, NW, NS)) igemm_glds_
     store_tile<TO, FM, FN, true>(acc, m0 + wm * WTM, n0 + wn * WTN, lane, g, y, ep, st1, st2);
     frag_stats<FN, BN, NW>(st1, st2, wn * WTN, smem, m0 / BM, n0, ep.stats, ep.sld);
   } else {
-    store_tile<TO, FM, FN>(acc, m0 + wm * WTM, n0 + wn * WTN, lane, g, y, ep);
+    store_tile<TO, FM, FN, false, JOIN>(acc, m0 + wm * WTM, n0 + wn * WTN, lane, g, y, ep);
   }
 }
 
@@ -1422,6 +1480,16 @@ int launch_glds_vc(const void* x, const void* w, void* y, const ConvGeom& g, con
   unsigned* tix = sp > 1 ? ticket_slots(tiles * nph) : nullptr;
   if (sp > 1 && !tix) return -1;
   const dim3 grid((unsigned)(tiles * sp), nph);
+  if (ep.zmask) {   // the residual-join epilogue: its own instantiation (no virtual concat, no statistics; not the
+                    // 256 x 256 tile, whose plain form already fills the register file)
+    if constexpr (VC != 1 && BM * BN < 256 * 256) {
+      if (ep.stats) return -1;
+      hipLaunchKernelGGL((igemm_glds_kernel<TO, BM, BN, WM, WN, NW, NS, false, VC, true>), grid, dim3(NW * 64), 0, s,
+                         (const TO*)x, (const TO*)w, (TO*)y, g, ep, xb, wb, epi, sp, ws, tix, pt, xa, x2b);
+      return BM;
+    }
+    return -1;
+  }
   if (ep.stats)
     hipLaunchKernelGGL((igemm_glds_kernel<TO, BM, BN, WM, WN, NW, NS, true, VC>), grid, dim3(NW * 64), 0, s,
                        (const TO*)x, (const TO*)w, (TO*)y, g, ep, xb, wb, epi, sp, ws, tix, pt, xa, x2b);

@@ -258,7 +258,7 @@ thread_local long long t_pw_rows = -1;
 template <typename TO>
 int launch_pw(int fj, const void* x, const void* w, void* y, const ConvGeom& g, const Epi<TO>& ep, hipStream_t s,
               float* ws, const PhaseTab* ph, const void* x2) {
-  if (g_knobs[13] < 0 || ws || ph || x2 || !g.aident || !g.oident || ep.y2 || ep.rmask) return -1;
+  if (g_knobs[13] < 0 || ws || ph || x2 || !g.aident || !g.oident || ep.y2 || ep.rmask || ep.zmask) return -1;
   if ((g.C != 64 && g.C != 128) || g.ldx < g.C || g.ldx % 8 || g.ldw != g.C || g.K % 64 || g.ldy % 8) return -1;
   if (ep.res && (ep.ldr % 4 || ep.ldr < g.K)) return -1;
   if (ep.stats && (ep.scale || ep.res || ep.aux)) return -1;   // host contract (conv.hip)

@@ -8,6 +8,15 @@ int launch_igemm(const void* x, const void* w, void* y, const ConvGeom& g, const
                  hipStream_t s) {
   const long long tiles = ((g.M + BM - 1) / BM) * ((g.K + BN - 1) / BN);
   const dim3 grid((unsigned)tiles, (unsigned)splits);
+  if (ep.zmask) {   // the residual-join epilogue (Epi::zmask): its own instantiation, unsplit, no statistics
+    if (ep.stats || splits > 1) return -1;
+    if constexpr (sizeof(T) == sizeof(TO))
+      hipLaunchKernelGGL((igemm_kernel<T, TO, BM, BN, WM, WN, false, false, true>), grid, dim3(256), 0, s, (const T*)x,
+                         (const T*)w, (TO*)y, g, ep, splits, ws);
+    else
+      return -1;
+    return BM;
+  }
   if (splits > 1) (void)hipMemsetAsync(ws, 0, sizeof(float) * g.M * g.K, s);
   if (ep.stats) {
     if constexpr (sizeof(T) == sizeof(TO))

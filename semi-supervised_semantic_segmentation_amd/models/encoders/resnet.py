@@ -24,6 +24,10 @@ class Bottleneck(nn.Module):
         self.bn3 = snn.BatchNorm2d(width * 4)
         self.relu = nn.ReLU(inplace=True)
         self.downsample = downsample
+        # the output is read only by the next block's conv1 and identity shortcut (set by the encoder on every block of a
+        # layer but the last): that conv1's input-gradient launch then adds the shortcut gradient and applies this block's
+        # final ReLU backward, and bn3's backward reads no residual and writes no shortcut gradient (snn.set_bn_join)
+        self.join_use = False
 
     def forward(self, x):
         if self.downsample is not None:
@@ -37,7 +41,8 @@ class Bottleneck(nn.Module):
         h = snn.GradHandoff() if self.downsample is None else None
         y = snn.conv_bn_act(self.conv1, x, self.bn1, grad_in=h, single_use=True)
         y = snn.conv_bn_act(self.conv2, y, self.bn2, single_use=True)
-        return snn.conv_bn_act(self.conv3, y, self.bn3, relu=True, residual=shortcut, grad_out=h)
+        return snn.conv_bn_act(self.conv3, y, self.bn3, relu=True, residual=shortcut, grad_out=h,
+                               join_use=self.join_use)
 
 
 class Stem(nn.Sequential):
@@ -67,6 +72,8 @@ class ResNetEncoder(nn.Module):
             blocks = [Bottleneck(inplanes, width, stride, down)]
             inplanes = width * 4
             blocks += [Bottleneck(inplanes, width) for _ in range(n - 1)]
+            for b in blocks[:-1]:   # (the last block's output also feeds the next layer's projection and the decoder)
+                b.join_use = True
             if i == 0:
                 blocks = [snn.MaxPool2d(3, 2, 1)] + blocks
             stages.append(Stage(*blocks))

@@ -25,7 +25,8 @@ _CFG = {'act_mask': os.environ.get('SSSEG_ACT_MASK', '1') != '0',
         'grad_join': True, 'stem': os.environ.get('SSSEG_STEM', '1') != '0', 'phases': True, 'eval_bwd_y': True, 'dtype': torch.bfloat16, 'sync_bn': True,
         'fuse_stats': True, 'vcat': os.environ.get('SSSEG_VCAT', '1') != '0',
         'vpad': os.environ.get('SSSEG_VPAD', '1') != '0',
-        'bn_gstat': os.environ.get('SSSEG_BN_GSTAT', '1') != '0'}
+        'bn_gstat': os.environ.get('SSSEG_BN_GSTAT', '1') != '0',
+        'bn_join': os.environ.get('SSSEG_BN_JOIN', '1') != '0'}
 
 
 def set_bn_grad_stats(on):
@@ -34,6 +35,19 @@ def set_bn_grad_stats(on):
     (ssseg_conv_igemm_epi_actmask with stats), so the BN backward skips its reduction pass over dy and x (default
     on)."""
     _CFG['bn_gstat'] = bool(on)
+
+
+def set_bn_join(on):
+    """A residual join act(bn(conv(..)) + shortcut) whose output feeds only the next block's first conv and shortcut
+    (conv_bn_act(..., join_use=True)): that conv's input-gradient launch adds the shortcut gradient and applies the join's
+    ReLU backward in its epilogue (ssseg_conv_igemm_epi_join), so the join's BN backward reads no residual (it rebuilt
+    the ReLU mask from it in both of its passes) and writes no shortcut gradient: the masked gradient it receives is
+    that gradient (default on; off with set_bn_grad_stats(False) as well)."""
+    _CFG['bn_join'] = bool(on)
+
+
+def _bn_join_on():
+    return _CFG['bn_join'] and _CFG['bn_gstat'] and _CFG['act_mask']
 
 
 def set_virtual_concat(on):
@@ -631,6 +645,7 @@ class _ConvFn(torch.autograd.Function):
         ctx.mod, ctx.relu, ctx.handoff, ctx.join, ctx.vcat = mod, relu, handoff, join, _vcat_of(x)
         ctx.xmask = x.__dict__.get('_ssseg_act_out')   # x = a single-use activation output: mask in our dgrad
         ctx.xgstat = x.__dict__.get('_ssseg_gstat')   # ... of a training BN: its backward sums in our dgrad too
+        ctx.xjoin = x.__dict__.get('_ssseg_join_out')   # x = a residual join's output read by us and the next shortcut
         ctx.save_for_backward(x, y if _act(relu)[0] else None)
         if _act(relu)[0] == ACT_RELU:
             # a ReLU output: a consumer's input-gradient launch may apply this ReLU's backward in place (the
@@ -654,14 +669,31 @@ class _ConvFn(torch.autograd.Function):
         # discriminator under the student's adversarial term, stays frozen in its backward whatever its flag is now)
         mod._ssseg_wgrad(x, gy, want=(ctx.needs_input_grad[1], ctx.needs_input_grad[2]))
         joined, last = _join_take(ctx.join)
-        pending = _sum_pending(_take(ctx.handoff), joined)
+        handed = _take(ctx.handoff)
+        pending = _sum_pending(handed, joined)
         if not ctx.needs_input_grad[0]:
             dx = None
         else:
-            dx = _masked_dgrad(mod, gy, x, ctx.xmask, ctx.xgstat, pending, ctx.vcat)
+            dx = _join_dgrad(mod, gy, x, ctx.xjoin, handed, joined, ctx.vcat)
+            if dx is None:
+                dx = _masked_dgrad(mod, gy, x, ctx.xmask, ctx.xgstat, pending, ctx.vcat)
             if dx is None:
                 dx = _dgrad_acc(mod, gy, x.shape, pending, ctx.vcat)
         return _join_give(ctx.join, last, dx), None, None, None, None, None, None, None
+
+
+def _join_dgrad(conv, gy, x, xjoin, handed, joined, vc):
+    """The input gradient of a conv whose input x is a residual join's output read only by this conv and the next
+    join's shortcut (xjoin, published by the producer: conv_bn_act(..., join_use=True)), with that shortcut's gradient
+    `handed` over through the GradHandoff: the epilogue adds it and applies the join's ReLU backward
+    (ssseg_conv_igemm_epi_join).  The result is the complete masked gradient of x: the join's BN backward takes it as
+    dy (no activation, no residual read) and as the shortcut gradient (no second output).  None where it does not
+    apply or the engine cannot (the caller runs the plain path)."""
+    if not (xjoin and handed is not None and joined is None and vc is None and _bn_join_on()
+            and getattr(conv, '_ssseg_join_dgrad_ok', lambda: False)() and handed.shape == x.shape
+            and handed.dtype == x.dtype):
+        return None
+    return conv._ssseg_dgrad(gy, x.shape, residual=handed, join=x)   # (not premasked: the engine declined)
 
 
 def _masked_dgrad(conv, gy, x, xmask, xgstat, pending, vc):
@@ -780,11 +812,15 @@ class _ConvBase:
             _PACK_EPOCH[0] += 1
         return t
 
-    def _igemm(self, x, w, y, desc, out_dt, bias=None, relu=False, fold=None, stats=None, stem=False, mask=None):
+    def _igemm(self, x, w, y, desc, out_dt, bias=None, relu=False, fold=None, stats=None, stem=False, mask=None,
+               join=None):
         """One engine launch; epilogue y = act(acc*scale + shift + residual) with shift = bias, or
         fold = (scale, shift, residual, aux) from a folded eval BatchNorm (conv_bn_act); aux, when given,
         receives the raw accumulator (the pre-BN activation the differentiated eval pass needs).
-        stem: the image-input kernel (ssseg_conv_stem_epi, w = the Cp-4 pack)."""
+        stem: the image-input kernel (ssseg_conv_stem_epi, w = the Cp-4 pack).
+        join = z: the residual-join input gradient (ssseg_conv_igemm_epi_join; the residual is the pending shortcut
+        gradient, z the conv's own forward input); returns False -- nothing launched -- where the engine cannot take
+        it."""
         dref = ctypes_ref(desc)
         nb = N.lib().ssseg_conv_igemm_workspace_bytes(dref, N.dt_code(x)) if (w is not None and not stem) else 0
         ws = N.workspace(nb, x.device) if nb else None
@@ -797,7 +833,13 @@ class _ConvBase:
                             N.dev_ptr(res) if res is not None else None, res.shape[1] if res is not None else 0,
                             N.dev_ptr(aux) if aux is not None else None, *_act(relu), *sf)
         vc = _vcat_of(x)
-        if mask is not None:
+        if join is not None:
+            if vc is not None or w is None or not N.call_or_unsupported(
+                    'ssseg_conv_igemm_epi_join', N.dev_ptr(x), N.dev_ptr(w), N.dev_ptr(y), dref, N.dt_code(x), out_dt,
+                    ctypes_ref(ep), N.dev_ptr(join), join.shape[1], N.dev_ptr(ws) if ws is not None else None, nb,
+                    N.stream()):
+                return False
+        elif mask is not None:
             if vc is not None:
                 materialize(x)
             N.call('ssseg_conv_igemm_epi_actmask', N.dev_ptr(x), N.dev_ptr(w) if w is not None else None,
@@ -818,6 +860,7 @@ class _ConvBase:
                    N.dt_code(x), out_dt, ctypes_ref(ep), N.dev_ptr(ws) if ws is not None else None, nb, N.stream())
         if stats is not None:
             stats.commit()
+        return True
 
     def _fold(self, bn, residual, cout, aux=None):
         """Eval BatchNorm (+ this conv's bias) as the epilogue's per-channel affine.  Returns the epilogue
@@ -1086,12 +1129,21 @@ class Conv2d(nn.Conv2d, _ConvBase):
         # (at most 4 output phases: _masked_dgrad sizes the statistics table for that many phase tails)
         return (sh == 1 and sw == 1) or (R >= sh and S >= sw and sh * sw <= 4 and self.dilation in (1, (1, 1)))
 
-    def _ssseg_dgrad(self, gy, xshape, residual=None, mask=None, stats=None, scale=None):
+    def _ssseg_join_dgrad_ok(self):
+        """The residual-join input gradient: a dense stride-1 conv (one launch over every input pixel)."""
+        return self._ssseg_mask_dgrad_ok() and self.stride == (1, 1)
+
+    def _ssseg_dgrad(self, gy, xshape, residual=None, mask=None, stats=None, scale=None, join=None):
         """dx of the conv; `residual` (a pending gradient of x, GradHandoff) is added in the epilogue; `mask` = (y,
         act, slope): x was the activation output y of its producer, whose backward the epilogue applies in place;
         `stats` (with mask, a StatRows): the epilogue also writes that producer BN's backward sums (gradient
         statistics rows, ssseg_conv_igemm_epi_actmask); `scale` (with mask): per-channel factor of the stored value
-        (a folded eval BN producer's scale: dx is that producer's conv-output gradient)."""
+        (a folded eval BN producer's scale: dx is that producer's conv-output gradient).  `join` (x itself, with residual
+        and a stride-1 conv; _igemm): x was a residual join's output -- dx is its complete masked gradient
+        (_ssseg_premasked set) unless the engine declines, then the plain dx + residual."""
+        if join is not None and (residual is None or mask is not None or stats is not None or scale is not None
+                                 or self.stride != (1, 1)):
+            raise ValueError('ssseg.nn.Conv2d: the residual-join input gradient needs the pending gradient and stride 1')
         if (stats is not None or scale is not None) and (mask is None or residual is not None):
             raise ValueError('ssseg.nn.Conv2d: gradient statistics / scale need the masked input gradient')
         fold = (None, None, residual, None) if residual is not None else (
@@ -1119,7 +1171,13 @@ class Conv2d(nn.Conv2d, _ConvBase):
                       py=ph - (R - 1) * dh, px=pw - (S - 1) * dw, outH=H, outW=W, osy=1, osx=1, ooy=0, oox=0,
                       ldy=cin, ldw=R * S * ce)
             with timer:
-                self._igemm(gy, w, dx, d, N.dt_code(dx), fold=fold, mask=mask, stats=stats)
+                if join is not None:
+                    if self._igemm(gy, w, dx, d, N.dt_code(dx), fold=fold, join=join):
+                        dx.__dict__['_ssseg_premasked'] = True
+                    else:
+                        self._igemm(gy, w, dx, d, N.dt_code(dx), fold=fold)
+                else:
+                    self._igemm(gy, w, dx, d, N.dt_code(dx), fold=fold, mask=mask, stats=stats)
             return dx
         timer.__enter__()
         for (phy, ry0, rny, dly, qy) in _phases(sh, ph, R, H, dh):
@@ -1368,7 +1426,7 @@ def _pad16(C, dtype):
 
 class _BNFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, residual, mod, relu, handoff=None, pre=None, single_use=False):
+    def forward(ctx, x, weight, bias, residual, mod, relu, handoff=None, pre=None, single_use=False, join_use=False):
         C = mod.num_features
         n, cp, h, w = x.shape
         P = n * h * w
@@ -1427,6 +1485,11 @@ class _BNFn(torch.autograd.Function):
             # reduction pass
             y.__dict__['_ssseg_act_out'] = (ACT_RELU, 0.0)
             y.__dict__['_ssseg_gstat'] = (C, None, mod)
+        if (join_use and training and residual is not None and _act(relu)[0] == ACT_RELU and _bn_join_on()
+                and x.requires_grad):
+            # y feeds only the next block's first conv and shortcut (the caller's guarantee): that conv's input-gradient
+            # launch makes y's complete masked gradient (_join_dgrad)
+            y.__dict__['_ssseg_join_out'] = True
         return y
 
     @staticmethod
@@ -1447,6 +1510,8 @@ class _BNFn(torch.autograd.Function):
         pgrad = mod.weight is not None and ctx.needs_input_grad[1]   # forward-time requires_grad
         # the consumer's input-gradient launch applied the ReLU backward already (and may have written our sums)
         act = 0 if gy.__dict__.get('_ssseg_premasked', False) else _act(ctx.relu)[0]
+        if act == 0:
+            res_p = None   # (the residual only rebuilds the activation mask)
         gs = gy.__dict__.get('_ssseg_gstats')
         if gs is not None and ctx.training and gs.rows > 0 and gs.C == C and residual is None and act == 0:
             # (sum dy, sum dy * y) rows from that epilogue -> (sum dy, sum dy * x_hat) + (dgamma, dbeta); channels
@@ -1468,16 +1533,20 @@ class _BNFn(torch.autograd.Function):
             _comm.all_reduce_sum(sums)
         dx = new_act(n, cp, h, w, x.dtype, dev, zero=cp > _pad16(C, x.dtype))
         want_res = residual is not None and ctx.needs_input_grad[3]
-        dres = new_act(n, cp, h, w, x.dtype, dev, zero=cp > _pad16(C, x.dtype)) if want_res else None
+        # (a premasked gy is the residual's gradient as it stands)
+        premasked = act == 0 and _act(ctx.relu)[0] != 0
+        dres = new_act(n, cp, h, w, x.dtype, dev, zero=cp > _pad16(C, x.dtype)) if want_res and not premasked else None
         N.call('ssseg_bn_bwd_apply', N.dev_ptr(gy), N.dev_ptr(x), res_p, N.dev_ptr(dx),
                N.dev_ptr(dres) if dres is not None else None, P, C, cp, cp, cp, cp, N.dev_ptr(mean),
                N.dev_ptr(invstd), N.dev_ptr(wt) if wt is not None else None,
                N.dev_ptr(bs) if bs is not None else None, act, int(bool(ctx.training)),
                N.dev_ptr(sums), float(count), N.dt_code(x), N.stream())
+        if want_res and premasked:
+            dres = gy
         if dres is not None and ctx.handoff is not None:
             ctx.handoff.put(dres)
             dres = None
-        return dx, None, None, dres, None, None, None, None, None
+        return dx, None, None, dres, None, None, None, None, None, None
 
 
 class BatchNorm2d(nn.BatchNorm2d):
@@ -1505,7 +1574,7 @@ class _ConvBNEvalFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, cweight, cbias, gamma, beta, residual, conv, bn, relu, grad_in=None, grad_out=None, join=None,
-                single_use=False):
+                single_use=False, join_use=False):
         # without a residual, y itself carries the pre-activation wherever the gradient survives the activation:
         # no raw accumulator copy (ssseg_bn_eval_bwd_grad_y recovers x_hat from y)
         ycopy = residual is None and _CFG['eval_bwd_y']
@@ -1516,6 +1585,11 @@ class _ConvBNEvalFn(torch.autograd.Function):
         ctx.grad_in, ctx.grad_out, ctx.join, ctx.vcat = grad_in, grad_out, join, _vcat_of(x)
         ctx.xmask = x.__dict__.get('_ssseg_act_out')   # x = a single-use BN+ReLU output: its backward in our dgrad
         ctx.xgstat = x.__dict__.get('_ssseg_gstat')
+        ctx.xjoin = x.__dict__.get('_ssseg_join_out')
+        if join_use and aux is not None and residual is not None and _act(relu)[0] == ACT_RELU and _bn_join_on():
+            # y feeds only the next block's first conv and shortcut: that conv's input-gradient launch makes y's complete
+            # masked gradient (_join_dgrad)
+            y.__dict__['_ssseg_join_out'] = True
         if (single_use and aux is None and residual is None and _act(relu)[0] == ACT_RELU and _CFG['bn_gstat']
                 and shift is not None):
             # y feeds exactly one conv: that conv's input-gradient launch applies this ReLU's backward and this BN's
@@ -1539,9 +1613,11 @@ class _ConvBNEvalFn(torch.autograd.Function):
         pre = (gs is not None and gy.__dict__.get('_ssseg_prescaled', False) and aux is None and not ctx.has_res
                and gs.rows > 0 and gs.C == C)
         act = 0 if gy.__dict__.get('_ssseg_premasked', False) else _act(ctx.relu)[0]
+        premasked = act == 0 and _act(ctx.relu)[0] != 0   # gy is the residual's gradient as it stands
         dconv = gy if pre else new_act(n, cp, h, w, y.dtype, dev, zero=cp > _pad16(C, y.dtype))
         want_res = ctx.has_res and ctx.needs_input_grad[5]
-        dres = new_act(n, cp, h, w, y.dtype, dev, zero=cp > _pad16(C, y.dtype)) if want_res else None
+        dres = (new_act(n, cp, h, w, y.dtype, dev, zero=cp > _pad16(C, y.dtype)) if want_res and not premasked
+                else None)
         sums = torch.empty(2 * C, dtype=torch.float64, device=dev)
         nb = N.lib().ssseg_bn_workspace_bytes(C)
         ws = N.workspace(nb, dev)
@@ -1601,20 +1677,27 @@ class _ConvBNEvalFn(torch.autograd.Function):
             _ready(*[p for p in (bn.weight, bn.bias) if want(p)])
         conv._ssseg_wgrad(x, dconv, bias_grad=False, want=(ctx.needs_input_grad[1], False))
         joined, last = _join_take(ctx.join)
-        pending = _sum_pending(_take(ctx.grad_in), joined)
+        handed = _take(ctx.grad_in)
+        pending = _sum_pending(handed, joined)
         if not ctx.needs_input_grad[0]:
             dx = None
         else:
-            dx = _masked_dgrad(conv, dconv, x, ctx.xmask, ctx.xgstat, pending, ctx.vcat)
+            dx = _join_dgrad(conv, dconv, x, ctx.xjoin, handed, joined, ctx.vcat)
+            if dx is None:
+                dx = _masked_dgrad(conv, dconv, x, ctx.xmask, ctx.xgstat, pending, ctx.vcat)
             if dx is None:
                 dx = _dgrad_acc(conv, dconv, x.shape, pending, ctx.vcat)
+        if want_res and premasked:
+            dres = gy
         if dres is not None and ctx.grad_out is not None:
             ctx.grad_out.put(dres)
             dres = None
-        return _join_give(ctx.join, last, dx), None, None, None, None, dres, None, None, None, None, None, None, None
+        return (_join_give(ctx.join, last, dx), None, None, None, None, dres, None, None, None, None, None, None, None,
+                None)
 
 
-def conv_bn_act(conv, x, bn, relu=True, residual=None, grad_in=None, grad_out=None, single_use=False):
+def conv_bn_act(conv, x, bn, relu=True, residual=None, grad_in=None, grad_out=None, single_use=False,
+                join_use=False):
     """act(bn(conv(x)) [+ residual]).  With an eval-mode BatchNorm the BN, residual add and ReLU run in
     the conv's epilogue (ssseg_bn_fold + ssseg_conv_igemm_epi): one kernel, each activation written once.
     Without gradients (the teacher forwards, reference train.py:69-94) that is all; when the eval pass
@@ -1624,7 +1707,12 @@ def conv_bn_act(conv, x, bn, relu=True, residual=None, grad_in=None, grad_out=No
     a block's first conv and its residual join) fuse the shortcut gradient into the first conv's dgrad.
     single_use: the caller guarantees the output feeds exactly one ssseg conv (Bottleneck bn1 -> conv2, bn2 -> conv3;
     a ConvBlock's first BN+ReLU): that conv's input gradient carries this BN's backward sums (training BN) or is
-    this conv's output gradient itself (differentiated eval BN: ReLU backward and BN scale applied in its epilogue)."""
+    this conv's output gradient itself (differentiated eval BN: ReLU backward and BN scale applied in its epilogue).
+    join_use (with residual and ReLU): the caller guarantees the output is read only by the next block's first conv
+    and by that block's shortcut, whose gradient reaches that conv through a GradHandoff (every ResNet Bottleneck of a
+    layer but the last): that conv's input-gradient launch then produces the output's complete masked gradient
+    (_join_dgrad), which this BN's backward takes as dy and as the shortcut gradient: no residual read, no second
+    output."""
     fusable = (isinstance(conv, (Conv2d, ConvTranspose2d)) and not conv._ssseg_head and isinstance(bn, BatchNorm2d)
                and not bn.training and bn.track_running_stats)
     if fusable:
@@ -1633,7 +1721,7 @@ def conv_bn_act(conv, x, bn, relu=True, residual=None, grad_in=None, grad_out=No
         if _no_grad(x, conv.weight, conv.bias, bn.weight, bn.bias, residual):
             return conv._ssseg_forward(x, relu, bn=bn, residual=residual)
         return _ConvBNEvalFn.apply(x, conv.weight, conv.bias, bn.weight, bn.bias, residual, conv, bn, relu, grad_in,
-                                   grad_out, _join_fwd(x), bool(single_use))
+                                   grad_out, _join_fwd(x), bool(single_use), bool(join_use))
     stats = None
     if (_CFG['fuse_stats'] and isinstance(conv, (Conv2d, ConvTranspose2d)) and isinstance(bn, BatchNorm2d)
             and (bn.training or not bn.track_running_stats) and bn.num_features == conv.out_channels and x.dim() == 4):
@@ -1644,16 +1732,17 @@ def conv_bn_act(conv, x, bn, relu=True, residual=None, grad_in=None, grad_out=No
         y = conv(x, handoff=grad_in, stats=stats)
     else:
         y = conv(x, stats=stats) if stats is not None else conv(x)
-    return bn_act(y, bn, relu=relu, residual=residual, grad_out=grad_out, pre=stats, single_use=single_use)
+    return bn_act(y, bn, relu=relu, residual=residual, grad_out=grad_out, pre=stats, single_use=single_use,
+                  join_use=join_use)
 
 
-def bn_act(x, bn, relu=True, residual=None, grad_out=None, pre=None, single_use=False):
+def bn_act(x, bn, relu=True, residual=None, grad_out=None, pre=None, single_use=False, join_use=False):
     """act(bn(x) [+ residual]) in one pass: ConvBlock's BN+ReLU (unet.py:9-10), Bottleneck's bn3+add+relu.
     pre: StatRows the producing conv's epilogue filled (fused training statistics)."""
     if not isinstance(bn, BatchNorm2d):
         raise TypeError('ssseg.nn.bn_act needs an ssseg BatchNorm2d')
     _need_act(x, rup(bn.num_features, vec()), 'BatchNorm2d')
-    return _BNFn.apply(x, bn.weight, bn.bias, residual, bn, relu, grad_out, pre, bool(single_use))
+    return _BNFn.apply(x, bn.weight, bn.bias, residual, bn, relu, grad_out, pre, bool(single_use), bool(join_use))
 
 
 # ------------------------------------------------------------------------------------------------
