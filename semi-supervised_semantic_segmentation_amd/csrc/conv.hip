@@ -437,6 +437,15 @@ int dispatch_igemm(const void* x, const void* w, void* y, const ConvGeom& g, con
         const int hv = x2 && heuristic_variant(g) == 0 ? 5 : heuristic_variant(g);
         return run_variant<T, TO>(hv, x, w, y, g, ep, (unsigned)xb, (unsigned)wb, s, nullptr, ph, x2, (unsigned)x2b);
       }
+      // a cached or imported variant that cannot run this launch: its kernel family was switched off after the
+      // geometry was tuned (knob 11 / 13 / 15 = -1 in this process, or a table saved by a process that had it on), or
+      // an imported row names a kernel that does not apply here.  The heuristic's choice runs every launch.
+      if (r == -1 && g_knobs[4] == 0 && v != 0) {
+        int hv = x2 && heuristic_variant(g) == 0 ? 5 : heuristic_variant(g);
+        if ((g.C > g.ldx || S > 1) && (hv == 0 || hv >= 24)) hv = 14;
+        if (hv != v)
+          return run_variant<T, TO>(hv, x, w, y, g, ep, (unsigned)xb, (unsigned)wb, s, wsv, ph, x2, (unsigned)x2b);
+      }
       return r;
     }
   }
