@@ -357,6 +357,37 @@ int ssseg_sgd_step(float* param, float* grad, float* momentum_buf, uint16_t* bf1
  * finite steps.  state = [scale, tracker, found_inf, 1/scale] on the device. */
 int ssseg_amp_update(float* state, const float* sqnorm, float growth, float backoff, int interval,
                      ssseg_stream_t stream);
+/* The Adam family over the flat arenas, fused: torch.optim.Adam (no amsgrad / maximize) and the reference's
+ * optimizers/ -- AdaMod, DiffGrad, DiffMod (diffGrad's friction coefficient on AdaMod's bounded step) and Ranger
+ * (RAdam + Lookahead).  Two launches with fixed arguments per step, so one captured graph serves every step:
+ *
+ * ssseg_optim_prepare (one thread, fp64): state[0] (the step counter t, as a double) += 1; the gradient coefficient
+ *   min(1, max_norm/(sqrt(sqnorm[0])+1e-6)) (skipped when max_norm <= 0) times the loss-scale unscale amp_state[3]
+ *   (nullable, as in ssseg_sgd_step); the bias corrections 1-beta^t and the mode's step sizes; for Ranger N_sma, the
+ *   rectified (N_sma > nsma_threshold) or unrectified step size and the Lookahead decision t % k == 0.  With an
+ *   amp_state a non-finite sqnorm[0] sets the skip flag instead and leaves t unchanged (GradScaler semantics).
+ *   state: SSSEG_OPT_STATE_DOUBLES doubles on the device, zero before the first step; only state[0] is persistent.
+ * ssseg_optim_step (one float4 pass; n % 4 == 0 and 16-byte aligned arenas): g^ = coefficient * grad, then per mode
+ *   ADAM      g^ += wd*p; m, v; p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
+ *   ADAMOD    m, v; p -= wd*lr*p; eta = (lr*sqrt(bc2)/bc1) / (sqrt(v)+eps); s = beta3*s + (1-beta3)*eta;
+ *             p -= min(eta, s) * m
+ *   DIFFGRAD  g^ += wd*p; m, v; c = dfc(prev - g^); prev = g^; p -= (lr*sqrt(bc2)/bc1) * (m*c) / (sqrt(v)+eps)
+ *   DIFFMOD   m, v; c = dfc(prev - g^); prev = g^; then ADAMOD's update with m*c in place of m
+ *   RANGER    v, m; at t == 1 slow = p; p -= wd*lr*p; rectified: p -= step*lr * m / (sqrt(v)+eps), else
+ *             p -= step*lr * m; when t % k == 0: slow += alpha*(p - slow), p = slow (slow is touched on those steps
+ *             and the first only)
+ *   dfc(d) by version: 0: 1/(1+exp(-|d|))   1: 1/(1+exp(-d))   2: 9/(1+exp(-|d|/2)) - 4
+ *   exp_avg_lr (s), previous_grad (prev) and slow_buffer are needed by the modes that name them, NULL otherwise.
+ *   grad is not modified.  A skipped step (see above) touches nothing. */
+enum { SSSEG_OPT_ADAM = 0, SSSEG_OPT_ADAMOD = 1, SSSEG_OPT_DIFFGRAD = 2, SSSEG_OPT_DIFFMOD = 3, SSSEG_OPT_RANGER = 4 };
+#define SSSEG_OPT_STATE_DOUBLES 8
+int ssseg_optim_prepare(double* state, int mode, double lr, double beta1, double beta2, double weight_decay,
+                        double max_norm, int64_t k, double nsma_threshold, const float* sqnorm,
+                        const float* amp_state, ssseg_stream_t stream);
+int ssseg_optim_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* exp_avg_lr,
+                     float* previous_grad, float* slow_buffer, int64_t n, int mode, int version, double beta1,
+                     double beta2, double beta3, double eps, double weight_decay, double alpha, const double* state,
+                     ssseg_stream_t stream);
 /* y = x * s[0] (s a device scalar): the loss-scaled gradient entering the backward pass (fp16 mode). */
 int ssseg_scale_by(const float* x, const float* s, float* y, int64_t n, ssseg_stream_t stream);
 

@@ -30,11 +30,11 @@ def _writer(path, step):
 
 
 def attach_grad_scaler(optimizer, device):
-    """fp16 mode: the device-side GradScaler.  Only ssseg's fused SGD unscales by 1/S and skips a non-finite
-    step; any other optimizer would apply S-scaled gradients, so it is refused."""
-    if not isinstance(optimizer, soptim.SGD):
-        raise NotImplementedError(f'fp16 compute mode needs ssseg.optim.SGD (loss-scaled gradients are unscaled in '
-                                  f'its fused step); got {type(optimizer).__name__}')
+    """fp16 mode: the device-side GradScaler.  Only ssseg's fused steps (SGD, the Adam family) unscale by 1/S and
+    skip a non-finite step; any other optimizer would apply S-scaled gradients, so it is refused."""
+    if not isinstance(optimizer, (soptim.SGD, soptim.FusedOptimizer)):
+        raise NotImplementedError(f'fp16 compute mode needs ssseg.optim.SGD or the fused Adam family (loss-scaled '
+                                  f'gradients are unscaled in their fused step); got {type(optimizer).__name__}')
     optimizer.grad_scaler = amp.GradScaler(device)
     return optimizer.grad_scaler
 

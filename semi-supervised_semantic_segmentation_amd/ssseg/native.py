@@ -97,6 +97,8 @@ SIGS = {
     'ssseg_sigmoid_bwd': (i32, [vp, vp, vp, i64, vp]),
     'ssseg_sqnorm_accum': (i32, [vp, i64, vp, vp, sz, vp]),
     'ssseg_sgd_step': (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, vp, i32, vp, vp]),
+    'ssseg_optim_prepare': (i32, [vp, i32, f64, f64, f64, f64, f64, i64, f64, vp, vp, vp]),
+    'ssseg_optim_step': (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, f64, f64, f64, f64, f64, f64, vp, vp]),
     'ssseg_amp_update': (i32, [vp, vp, f32, f32, i32, vp]),
     'ssseg_scale_by': (i32, [vp, vp, vp, i64, vp]),
     # convolution engine
@@ -212,6 +214,8 @@ class NflParams(ctypes.Structure):
                [('from_logits', ctypes.c_int32), ('size_average', ctypes.c_int32)]
 
 
+OPT_ADAM, OPT_ADAMOD, OPT_DIFFGRAD, OPT_DIFFMOD, OPT_RANGER = range(5)
+OPT_STATE_DOUBLES = 8
 RED_NONE, RED_MEAN, RED_SUM = 0, 1, 2
 LOSS_REDUCE, LOSS_OHEM, LOSS_NFL, LOSS_DICE_LOGITS, LOSS_DICE_PROB = 0, 1, 2, 3, 4
 

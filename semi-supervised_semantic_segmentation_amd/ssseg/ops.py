@@ -280,6 +280,25 @@ def sgd_step_(param, grad, buf, shadow, lr, momentum, wd, max_norm, sqnorm, firs
            N.dev_ptr(amp_state) if amp_state is not None else None, N.stream())
 
 
+def optim_prepare_(state, mode, lr, beta1, beta2, wd, max_norm, k=1, nsma_threshold=0.0, sqnorm=None, amp_state=None):
+    """Per-step scalars of the fused Adam family (step counter, clip / unscale, bias corrections, Ranger's
+    decisions) computed on the device into `state` (fp64, native.OPT_STATE_DOUBLES)."""
+    assert state.dtype == torch.float64 and state.numel() >= N.OPT_STATE_DOUBLES
+    N.call('ssseg_optim_prepare', N.dev_ptr(state, 'state'), int(mode), float(lr), float(beta1), float(beta2),
+           float(wd), float(max_norm), int(k), float(nsma_threshold),
+           N.dev_ptr(sqnorm) if sqnorm is not None else None,
+           N.dev_ptr(amp_state) if amp_state is not None else None, N.stream())
+
+
+def optim_step_(param, grad, exp_avg, exp_avg_sq, exp_avg_lr, previous_grad, slow_buffer, mode, version, beta1, beta2,
+                beta3, eps, wd, alpha, state):
+    """One pass of the fused Adam-family update over the flat arenas, from the scalars optim_prepare_ left."""
+    N.call('ssseg_optim_step', N.dev_ptr(param, 'param'), N.dev_ptr(grad, 'grad'), N.dev_ptr(exp_avg, 'exp_avg'),
+           N.dev_ptr(exp_avg_sq, 'exp_avg_sq'), N.dev_ptr(exp_avg_lr), N.dev_ptr(previous_grad),
+           N.dev_ptr(slow_buffer), param.numel(), int(mode), int(version), float(beta1), float(beta2), float(beta3),
+           float(eps), float(wd), float(alpha), N.dev_ptr(state, 'state'), N.stream())
+
+
 # ------------------------------------------------------------------------------------------------
 # Lovász (losses.py:239-250)
 # ------------------------------------------------------------------------------------------------

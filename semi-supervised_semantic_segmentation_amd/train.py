@@ -23,7 +23,7 @@ import utils.utils as utils
 from ssseg import nn as snn
 from ssseg import ops
 from ssseg.ddp import DistributedDataParallel as _DDP
-from ssseg.optim import SGD as _SGD
+from ssseg.optim import SGD as _SGD, FusedOptimizer as _Fused
 
 
 def _inner(model):
@@ -281,7 +281,7 @@ def train_step(model, ema_model, optimizer, image, mask, unsup_a, unsup_b, epoch
         ddp.finish()
     if step % tc['virtual_batch_size_multiplier'] == 0 and step != 0:
         clip = tc['gradient_clip_value']
-        if isinstance(optimizer, _SGD):
+        if isinstance(optimizer, (_SGD, _Fused)):
             optimizer.step(max_norm=clip)
         else:
             torch.nn.utils.clip_grad_norm_(_inner(model).parameters(), clip)
