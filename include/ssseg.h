@@ -117,6 +117,32 @@ int ssseg_rotate_fwd(const float* x, float* y, int64_t N, int64_t C, int64_t H, 
 int ssseg_rotate_bwd(const float* gy, float* gx, int64_t N, int64_t C, int64_t H, int64_t W, double angle_deg,
                      ssseg_stream_t stream);
 
+/* Per-sample affine warp (reversible_augmentations.RotateRescale: rotation and zoom about the image centre at a
+ * fixed size).  mats: [N][6] f32 in DEVICE memory, [a, b, tx, c, d, ty] per sample, mapping an output pixel (x, y)
+ * to input coordinates sx = a x + b y + tx, sy = c x + d y + ty, evaluated as fmaf(a, x, fmaf(b, y, tx)); pixel
+ * centres on integers, bilinear, taps outside the image are zero.  For angle th (degrees, counter-clockwise, the
+ * sense of ssseg_rotate_fwd) and zoom s, with cx = (W-1)/2, cy = (H-1)/2, al = cos th / s, be = -sin th / s:
+ *   A(th, s) = [al, be, cx - al cx - be cy;  -be, al, cy + be cx - al cy],   A(th, s)^-1 = A(-th, 1/s);
+ * A(0, 1) = [1,0,0; 0,1,0] copies x bit for bit.  Strides (elements) and dt (f32 / bf16 / f16) as in
+ * ssseg_bilinear_fwd: NCHW and channels-last; fp32 accumulation.  valid_out (nullable): [N,H,W] f32, 1 where
+ * 0 <= sx <= W-1 and 0 <= sy <= H-1, else 0. */
+int ssseg_affine_warp_fwd(const void* x, void* y, const float* mats, int64_t N, int64_t C, int64_t H, int64_t W,
+                          const int64_t* x_strides4_host, const int64_t* y_strides4_host, int dt, float* valid_out,
+                          ssseg_stream_t stream);
+/* gx = (d y / d x)^T gy, the exact adjoint as a deterministic gather (no atomics, no memset; gx overwritten): every
+ * input pixel p sums, in row-major order, the gradients of the output pixels that tapped it, searched in the box
+ * around mats_inv p with half-extents |ia|+|ib|+1 and |ic|+|id|+1 (mats_inv: the inverse matrices, same layout). */
+int ssseg_affine_warp_bwd(const void* gy, void* gx, const float* mats, const float* mats_inv, int64_t N, int64_t C,
+                          int64_t H, int64_t W, const int64_t* gy_strides4_host, const int64_t* gx_strides4_host,
+                          int dt, ssseg_stream_t stream);
+/* Draws th_b ~ U(-max_angle_deg, max_angle_deg) and s_b ~ U(scale_lo, scale_hi) per sample (the reference's Rotate /
+ * Rescale distributions) and writes A(th_b, s_b) to mats and its inverse to mats_inv ([B][6] f32, device).  Philox
+ * keyed by seed at counter *offset_dev + b (stream 2 of the key: disjoint from the CowMix draws of the same counter);
+ * the counter is read from device memory and advanced there by B, so a captured HIP graph replays fresh draws. */
+int ssseg_affine_draw_dev(float* mats, float* mats_inv, int64_t B, int64_t H, int64_t W, double max_angle_deg,
+                          double scale_lo, double scale_hi, uint64_t seed, unsigned long long* offset_dev,
+                          ssseg_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Train-time augmentations on the device (reference configs/default_config.py:179-212: the albumentations
  * ReplayCompose pipelines the reference datasets apply per sample, data/dataset.py:71-74,
@@ -182,6 +208,14 @@ int ssseg_consistency_fwd(const float* s, const float* t, int64_t B, int64_t C, 
 /* gs = 2 (sig(s)-sig(t)) sig(s)(1-sig(s)) cm / sum(cm) * gout[0]  (sum(cm) read from out3[2]) */
 int ssseg_consistency_bwd(const float* s, const float* t, int64_t B, int64_t C, int64_t HW, float thr,
                           const float* out3, const float* gout, float* gs, ssseg_stream_t stream);
+/* The same loss with a per-pixel weight w [B,HW] f32 multiplying the confidence modulator cm (the validity map of
+ * ssseg_affine_warp_fwd for a warped-back student view):
+ * out[0] = sum(d^2 cm w) / sum(cm w) (NaN on 0/0);  out[1] = sum(cm w) / (B HW);  out[2] = sum(cm w).
+ * The device code is shared with the unweighted entry points; w == 1 everywhere gives their results bit for bit. */
+int ssseg_consistency_w_fwd(const float* s, const float* t, const float* w, int64_t B, int64_t C, int64_t HW,
+                            float thr, float* out3, void* ws, size_t ws_bytes, ssseg_stream_t stream);
+int ssseg_consistency_w_bwd(const float* s, const float* t, const float* w, int64_t B, int64_t C, int64_t HW,
+                            float thr, const float* out3, const float* gout, float* gs, ssseg_stream_t stream);
 
 /* Binary Lovász (losses.binary_lovasz_loss_with_logits losses.py:239-250 -> lovasz_softmax
  * lovasz.py:155-201 with classes=[1], per_image=True).  logits, target [B,C,HW] f32, 1 <= B <= 4096.

@@ -101,8 +101,11 @@ __global__ void bce_bwd_kernel(const float* x, const float* t, int64_t n, const 
 }
 
 // ---- consistency loss ----
-__global__ void __launch_bounds__(RED_THREADS) cons_partial_kernel(const float* s, const float* t, int64_t C,
-                                                                   int64_t HW, int64_t npix, float thr,
+// WEIGHTED: the confidence modulator is multiplied by w[b][pix] (ssseg_consistency_w_*: the validity map of the
+// warped-back student view); the unweighted instantiation is the code it always was, and w == 1 gives its bits
+template <bool WEIGHTED>
+__global__ void __launch_bounds__(RED_THREADS) cons_partial_kernel(const float* s, const float* t, const float* w,
+                                                                   int64_t C, int64_t HW, int64_t npix, float thr,
                                                                    double* part) {
   __shared__ double red[RED_THREADS / 64];
   double num = 0.0, cnt = 0.0;
@@ -119,8 +122,14 @@ __global__ void __launch_bounds__(RED_THREADS) cons_partial_kernel(const float* 
       mx = fmaxf(mx, pt);
     }
     if (mx > thr) {
-      num += (double)d2;
-      cnt += 1.0;
+      if (WEIGHTED) {
+        const double cmw = (double)w[q];
+        num += (double)d2 * cmw;
+        cnt += cmw;
+      } else {
+        num += (double)d2;
+        cnt += 1.0;
+      }
     }
   }
   num = block_sum(num, red);
@@ -148,8 +157,9 @@ __global__ void __launch_bounds__(RED_THREADS) cons_final_kernel(const double* p
   }
 }
 
-__global__ void cons_bwd_kernel(const float* s, const float* t, int64_t C, int64_t HW, int64_t npix, float thr,
-                                const float* out3, const float* gout, float* gs) {
+template <bool WEIGHTED>
+__global__ void cons_bwd_kernel(const float* s, const float* t, const float* w, int64_t C, int64_t HW, int64_t npix,
+                                float thr, const float* out3, const float* gout, float* gs) {
   const float scale = gout[0] / out3[2];
   for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < npix; q += (int64_t)gridDim.x * blockDim.x) {
     const int64_t b = q / HW, pix = q % HW;
@@ -157,7 +167,7 @@ __global__ void cons_bwd_kernel(const float* s, const float* t, int64_t C, int64
     const float* tp = t + b * C * HW + pix;
     float mx = -INFINITY;
     for (int64_t c = 0; c < C; ++c) mx = fmaxf(mx, sigmoidf_ref(tp[c * HW]));
-    const float cm = mx > thr ? 1.f : 0.f;
+    const float cm = mx > thr ? (WEIGHTED ? w[q] : 1.f) : 0.f;
     float* gp = gs + b * C * HW + pix;
     for (int64_t c = 0; c < C; ++c) {
       const float ps = sigmoidf_ref(sp[c * HW]);
@@ -462,27 +472,51 @@ extern "C" int ssseg_bce_logits_bwd(const float* x, const float* t, int64_t n, c
   return 0;
 }
 
-extern "C" int ssseg_consistency_fwd(const float* s, const float* t, int64_t B, int64_t C, int64_t HW, float thr,
-                                     float* out3, void* ws, size_t ws_bytes, ssseg_stream_t stream) {
-  if (!s || !t || !out3 || B <= 0 || C <= 0 || HW <= 0) return SSSEG_EINVAL;
+static int consistency_fwd(const float* s, const float* t, const float* w, bool weighted, int64_t B, int64_t C,
+                           int64_t HW, float thr, float* out3, void* ws, size_t ws_bytes, ssseg_stream_t stream) {
+  if (!s || !t || !out3 || (weighted && !w) || B <= 0 || C <= 0 || HW <= 0) return SSSEG_EINVAL;
   if (!ws || ws_bytes < ssseg_reduce_workspace_bytes(B * HW)) return SSSEG_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const int64_t npix = B * HW;
   const int nb = red_blocks(npix);
-  hipLaunchKernelGGL(cons_partial_kernel, dim3(nb), dim3(RED_THREADS), 0, st, s, t, C, HW, npix, thr, (double*)ws);
+  hipLaunchKernelGGL(weighted ? cons_partial_kernel<true> : cons_partial_kernel<false>, dim3(nb), dim3(RED_THREADS), 0,
+                     st, s, t, w, C, HW, npix, thr, (double*)ws);
   hipLaunchKernelGGL(cons_final_kernel, dim3(1), dim3(RED_THREADS), 0, st, (const double*)ws, nb, npix, out3);
   SSSEG_LAUNCH_CHECK();
   return 0;
 }
 
-extern "C" int ssseg_consistency_bwd(const float* s, const float* t, int64_t B, int64_t C, int64_t HW, float thr,
-                                     const float* out3, const float* gout, float* gs, ssseg_stream_t stream) {
-  if (!s || !t || !out3 || !gout || !gs || B <= 0 || C <= 0 || HW <= 0) return SSSEG_EINVAL;
+static int consistency_bwd(const float* s, const float* t, const float* w, bool weighted, int64_t B, int64_t C,
+                           int64_t HW, float thr, const float* out3, const float* gout, float* gs,
+                           ssseg_stream_t stream) {
+  if (!s || !t || !out3 || !gout || !gs || (weighted && !w) || B <= 0 || C <= 0 || HW <= 0) return SSSEG_EINVAL;
   const int64_t npix = B * HW;
-  hipLaunchKernelGGL(cons_bwd_kernel, dim3(ssseg_grid(npix, 256)), dim3(256), 0, (hipStream_t)stream, s, t, C, HW,
-                     npix, thr, out3, gout, gs);
+  hipLaunchKernelGGL(weighted ? cons_bwd_kernel<true> : cons_bwd_kernel<false>, dim3(ssseg_grid(npix, 256)), dim3(256),
+                     0, (hipStream_t)stream, s, t, w, C, HW, npix, thr, out3, gout, gs);
   SSSEG_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int ssseg_consistency_fwd(const float* s, const float* t, int64_t B, int64_t C, int64_t HW, float thr,
+                                     float* out3, void* ws, size_t ws_bytes, ssseg_stream_t stream) {
+  return consistency_fwd(s, t, nullptr, false, B, C, HW, thr, out3, ws, ws_bytes, stream);
+}
+
+extern "C" int ssseg_consistency_bwd(const float* s, const float* t, int64_t B, int64_t C, int64_t HW, float thr,
+                                     const float* out3, const float* gout, float* gs, ssseg_stream_t stream) {
+  return consistency_bwd(s, t, nullptr, false, B, C, HW, thr, out3, gout, gs, stream);
+}
+
+extern "C" int ssseg_consistency_w_fwd(const float* s, const float* t, const float* w, int64_t B, int64_t C,
+                                       int64_t HW, float thr, float* out3, void* ws, size_t ws_bytes,
+                                       ssseg_stream_t stream) {
+  return consistency_fwd(s, t, w, true, B, C, HW, thr, out3, ws, ws_bytes, stream);
+}
+
+extern "C" int ssseg_consistency_w_bwd(const float* s, const float* t, const float* w, int64_t B, int64_t C,
+                                       int64_t HW, float thr, const float* out3, const float* gout, float* gs,
+                                       ssseg_stream_t stream) {
+  return consistency_bwd(s, t, w, true, B, C, HW, thr, out3, gout, gs, stream);
 }
 
 extern "C" int ssseg_ema_update(float* ema, const float* param, int64_t n, double alpha, ssseg_stream_t stream) {

@@ -55,11 +55,16 @@ SIGS = {
     'ssseg_aug_uniform_field': (i32, [vp, i64, u64, vp]),
     'ssseg_rotate_fwd': (i32, [vp, vp, i64, i64, i64, i64, f64, vp]),
     'ssseg_rotate_bwd': (i32, [vp, vp, i64, i64, i64, i64, f64, vp]),
+    'ssseg_affine_warp_fwd': (i32, [vp, vp, vp, i64, i64, i64, i64, I64P, I64P, i32, vp, vp]),
+    'ssseg_affine_warp_bwd': (i32, [vp, vp, vp, vp, i64, i64, i64, i64, I64P, I64P, i32, vp]),
+    'ssseg_affine_draw_dev': (i32, [vp, vp, i64, i64, i64, f64, f64, f64, u64, vp, vp]),
     'ssseg_reduce_workspace_bytes': (sz, [i64]),
     'ssseg_bce_logits_fwd': (i32, [vp, vp, i64, vp, vp, sz, vp]),
     'ssseg_bce_logits_bwd': (i32, [vp, vp, i64, vp, vp, vp]),
     'ssseg_consistency_fwd': (i32, [vp, vp, i64, i64, i64, f32, vp, vp, sz, vp]),
     'ssseg_consistency_bwd': (i32, [vp, vp, i64, i64, i64, f32, vp, vp, vp, vp]),
+    'ssseg_consistency_w_fwd': (i32, [vp, vp, vp, i64, i64, i64, f32, vp, vp, sz, vp]),
+    'ssseg_consistency_w_bwd': (i32, [vp, vp, vp, i64, i64, i64, f32, vp, vp, vp, vp]),
     'ssseg_lovasz_workspace_bytes': (sz, [i64, i64]),
     'ssseg_lovasz_fwd': (i32, [vp, vp, i64, i64, i64, vp, vp, sz, vp]),
     'ssseg_lovasz_bwd': (i32, [vp, vp, i64, i64, i64, vp, vp, vp, sz, vp]),

@@ -171,6 +171,66 @@ def rotate(x, angle_deg):
     return _Rotate.apply(x, angle_deg)
 
 
+def affine_mats(angles_deg, scales, H, W, device):
+    """Per-sample matrices of the affine warp (include/ssseg.h, ssseg_affine_warp_fwd): A(theta_b, s_b) and its
+    inverse A(-theta_b, 1/s_b), [B, 6] fp32 each, built on the host in fp64, rounded once and uploaded."""
+    th = torch.deg2rad(torch.as_tensor(angles_deg, dtype=torch.float64).reshape(-1).cpu())
+    s = torch.as_tensor(scales, dtype=torch.float64).reshape(-1).cpu()
+    if th.numel() != s.numel():
+        raise ValueError('affine_mats: one angle and one scale per sample')
+    cx, cy = (W - 1) / 2.0, (H - 1) / 2.0
+
+    def mat(al, be):
+        return torch.stack([al, be, cx - al * cx - be * cy, -be, al, cy + be * cx - al * cy], 1)
+    mats = mat(torch.cos(th) / s, -torch.sin(th) / s)
+    inv = mat(torch.cos(th) * s, torch.sin(th) * s)
+    return mats.float().to(device), inv.float().to(device)
+
+
+def _dense_like(x):
+    """an empty tensor of x's shape and dtype: channels-last where x is, NCHW otherwise"""
+    fmt = torch.channels_last if (x.is_contiguous(memory_format=torch.channels_last) and x.shape[1] > 1
+                                  and not x.is_contiguous()) else torch.contiguous_format
+    return torch.empty(tuple(x.shape), device=x.device, dtype=x.dtype, memory_format=fmt)
+
+
+class _AffineWarp(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, mats, mats_inv, want_valid):
+        Nn, C, H, W = x.shape
+        if tuple(mats.shape) != (Nn, 6) or tuple(mats_inv.shape) != (Nn, 6):
+            raise ValueError('affine_warp: mats and mats_inv must be [N, 6]')
+        mats, mats_inv = _c(mats.float()), _c(mats_inv.float())
+        y = _dense_like(x)
+        valid = torch.empty((Nn, H, W), device=x.device, dtype=torch.float32) if want_valid else None
+        N.call('ssseg_affine_warp_fwd', N.dev_ptr(x, 'x'), N.dev_ptr(y), N.dev_ptr(mats, 'mats'), Nn, C, H, W,
+               N.strides4(x), N.strides4(y), N.dt_code(x), N.dev_ptr(valid), N.stream())
+        ctx.save_for_backward(mats, mats_inv)
+        ctx.set_materialize_grads(False)   # no zero-filled gradient for the validity map
+        if not want_valid:
+            return y
+        ctx.mark_non_differentiable(valid)
+        return y, valid
+
+    @staticmethod
+    def backward(ctx, gy, g_valid=None):
+        if gy is None:
+            return None, None, None, None
+        mats, mats_inv = ctx.saved_tensors
+        Nn, C, H, W = gy.shape
+        gx = _dense_like(gy)
+        N.call('ssseg_affine_warp_bwd', N.dev_ptr(gy, 'gy'), N.dev_ptr(gx), N.dev_ptr(mats), N.dev_ptr(mats_inv), Nn, C,
+               H, W, N.strides4(gy), N.strides4(gx), N.dt_code(gy), N.stream())
+        return gx, None, None, None
+
+
+def affine_warp(x, mats, mats_inv, want_valid=False):
+    """y[n] = bilinear sample of x[n] at mats[n] applied to each output pixel (zeros outside), any of fp32 / bf16 /
+    fp16, NCHW or channels-last; differentiable in x (the gather adjoint ssseg_affine_warp_bwd, which needs
+    mats_inv).  want_valid: also the [N, H, W] fp32 map of the pixels whose sampling point lies in the image."""
+    return _AffineWarp.apply(x, mats, mats_inv, bool(want_valid))
+
+
 class _Sigmoid(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
@@ -225,16 +285,24 @@ def bce_with_logits_mean(x, t):
 
 class _Consistency(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, s, t, thr):
+    def forward(ctx, s, t, thr, w):
         s, t = _c(s.float()), _c(t.float())
         B, C = s.shape[:2]
         HW = s[0, 0].numel()
         out = torch.empty(3, device=s.device, dtype=torch.float32)
         nb = N.lib().ssseg_reduce_workspace_bytes(B * HW)
         ws = N.workspace(nb, s.device)
-        N.call('ssseg_consistency_fwd', N.dev_ptr(s, 'student'), N.dev_ptr(t, 'teacher'), B, C, HW, float(thr),
-               N.dev_ptr(out), N.dev_ptr(ws), nb, N.stream())
-        ctx.save_for_backward(s, t, out)
+        if w is None:
+            N.call('ssseg_consistency_fwd', N.dev_ptr(s, 'student'), N.dev_ptr(t, 'teacher'), B, C, HW, float(thr),
+                   N.dev_ptr(out), N.dev_ptr(ws), nb, N.stream())
+            ctx.save_for_backward(s, t, out)
+        else:
+            w = _c(w.float())
+            if w.numel() != B * HW:
+                raise ValueError('consistency_loss_weighted: w must hold one weight per pixel, [B, H, W]')
+            N.call('ssseg_consistency_w_fwd', N.dev_ptr(s, 'student'), N.dev_ptr(t, 'teacher'), N.dev_ptr(w, 'w'), B, C,
+                   HW, float(thr), N.dev_ptr(out), N.dev_ptr(ws), nb, N.stream())
+            ctx.save_for_backward(s, t, out, w)
         ctx.meta = (B, C, HW, float(thr))
         ctx.mark_non_differentiable(out)
         ctx.set_materialize_grads(False)   # no zero-filled gradient for the cm output (a framework fill kernel)
@@ -242,18 +310,29 @@ class _Consistency(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss, g_cm):
-        s, t, out = ctx.saved_tensors
+        s, t, out = ctx.saved_tensors[:3]
         B, C, HW, thr = ctx.meta
         gs = torch.empty_like(s)
         g = _c(g_loss.float())
-        N.call('ssseg_consistency_bwd', N.dev_ptr(s), N.dev_ptr(t), B, C, HW, thr, N.dev_ptr(out), N.dev_ptr(g),
-               N.dev_ptr(gs), N.stream())
-        return gs, None, None
+        if len(ctx.saved_tensors) == 3:
+            N.call('ssseg_consistency_bwd', N.dev_ptr(s), N.dev_ptr(t), B, C, HW, thr, N.dev_ptr(out), N.dev_ptr(g),
+                   N.dev_ptr(gs), N.stream())
+        else:
+            N.call('ssseg_consistency_w_bwd', N.dev_ptr(s), N.dev_ptr(t), N.dev_ptr(ctx.saved_tensors[3]), B, C, HW,
+                   thr, N.dev_ptr(out), N.dev_ptr(g), N.dev_ptr(gs), N.stream())
+        return gs, None, None, None
 
 
 def consistency_loss(student_logits, teacher_logits, thr):
     """train.py:97-108: returns (loss, confidence_modulator.mean()); loss is NaN when no pixel is confident."""
-    return _Consistency.apply(student_logits, teacher_logits, thr)
+    return _Consistency.apply(student_logits, teacher_logits, thr, None)
+
+
+def consistency_loss_weighted(student_logits, teacher_logits, w, thr):
+    """consistency_loss with the confidence modulator multiplied by w [B, H, W] (the validity map of a warped-back
+    student view): (sum d^2 cm w / sum cm w, sum cm w / npix); NaN when no weighted pixel is confident.  w is a
+    constant (no gradient)."""
+    return _Consistency.apply(student_logits, teacher_logits, thr, w)
 
 
 # ------------------------------------------------------------------------------------------------

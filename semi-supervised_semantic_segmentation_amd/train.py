@@ -151,16 +151,34 @@ def _teacher_targets(ema_model, unsup_a, unsup_b, tc):
     return mixed_ema_pred, mixed_images
 
 
+def _consistency_augmentation(tc):
+    """config['train']['consistency_augmentation']: a reversible_augmentations.RotateRescale, or a zero-argument
+    factory of one, called once (the instance takes its place in the config); None where the key is absent."""
+    aug = tc.get('consistency_augmentation')
+    if aug is not None and not hasattr(aug, 'reverse'):
+        aug = tc['consistency_augmentation'] = aug()
+    return aug
+
+
 def _consistency_forward(model, targets, tc, epoch):
     """train.py:87-112: the student's eval-mode forward on the mixed images (with grad), resized, and the weighted
     consistency loss.  Returns (unsup_loss, cm_mean)."""
     mixed_ema_pred, mixed_images = targets
+    aug = _consistency_augmentation(tc)
+    # geometric consistency (the reference's plan, train.py:16-17): the student sees a per-sample rotated / rescaled
+    # view, its prediction is warped back onto the teacher's frame, and the pixels that left the frame carry no weight
+    view = aug.apply([mixed_images])[0] if aug is not None else mixed_images
     model.eval()
     with snn.folded(_inner(model)):
-        student_pred = model(mixed_images)[-1][-1]
+        student_pred = model(view)[-1][-1]
     model.train()
     student_pred = ops.interpolate_bilinear(student_pred, mixed_images.shape[2:4], align_corners=False)
-    consistency, cm_mean = ops.consistency_loss(student_pred, mixed_ema_pred, tc['confidence_threshold'])
+    if aug is not None:
+        student_pred = aug.reverse([student_pred])[0]
+        consistency, cm_mean = ops.consistency_loss_weighted(student_pred, mixed_ema_pred, aug.valid,
+                                                             tc['confidence_threshold'])
+    else:
+        consistency, cm_mean = ops.consistency_loss(student_pred, mixed_ema_pred, tc['confidence_threshold'])
     # consistency * weight * float(epoch > 25) (train.py:112; a 0/0 NaN survives the 0.0 gate, as there)
     return ops.scale(consistency, float(tc['consistency_loss_weight']) * float(epoch > 25)), cm_mean
 
@@ -301,7 +319,8 @@ def train_step(model, ema_model, optimizer, image, mask, unsup_a, unsup_b, epoch
 # repeats the Python decisions of its capture, so the graph is keyed on every one of them: the optimizer step taken
 # or skipped (train.py:121, step % virtual_batch_size_multiplier), the epoch gate of the consistency weight
 # (train.py:112), every learning rate, the input geometry and compute dtype -- a new key captures a new graph (the two
-# most recent are kept).  Not captured (eager steps instead): CowMix drawn from the CPU generator (parity mode), steps
+# most recent are kept).  Not captured (eager steps instead): CowMix drawn from the CPU generator (parity mode), a
+# consistency augmentation whose parameters come from the host (source='cpu' or set_params), steps
 # with collectives on torch.distributed (gloo, or SSSEG_COMM=c10d: the native RCCL communicator's steps ARE captured),
 # the first optimizer step (SGD's momentum buffer starts from it),
 # and SSSEG_TRAIN_GRAPH=0.
@@ -324,6 +343,9 @@ def _graph_key(model, ema_model, optimizer, image, mask, unsup_a, unsup_b, epoch
         return None
     if tc['use_semi_supervised'] and cowmix.NOISE_SOURCE != 'device':
         return None
+    aug = _consistency_augmentation(tc) if tc['use_semi_supervised'] else None
+    if aug is not None and (aug.source != 'device' or aug.fixed is not None):
+        return None   # parameters drawn or uploaded on the host: a replay would repeat them
     if torch.distributed.is_initialized() and (_world() > 1 or getattr(model, '_active', False)):
         # collectives in the step (DDP buckets, SyncBN): capturable only on the native communicator (ssseg.comm; c10d's
         # Work objects and watchdog break a capture, gloo runs on the host) -- DESIGN.md §6

@@ -29,10 +29,10 @@ import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
 # semi-supervised step GFLOP per labelled image (3F sup fwd+bwd + 2F teacher + 3F consistency fwd+bwd)
-STEP_GFLOP_PER_IMAGE = {'c2': 765.1, 'c3': 3855.8, 'c4': 3904.2, 'c5': 85.2}
+STEP_GFLOP_PER_IMAGE = {'c2': 765.1, 'c2geo': 765.1, 'c3': 3855.8, 'c4': 3904.2, 'c5': 85.2}   # (c2geo: the same convs)
 PEAK = {'bfloat16': 2.5e15, 'float16': 2.5e15, 'float32': 0.16e15}   # dense MFMA (MI355X_MICROARCH.md)
-CFGS = {'c2': 'configs/c2_unet_r50.py', 'c3': 'configs/c3_deeplabv3_r101.py', 'c4': 'configs/c4_msa_hrnet.py',
-        'c5': 'configs/c5_hardnet_disc.py'}
+CFGS = {'c2': 'configs/c2_unet_r50.py', 'c2geo': 'configs/c2_unet_r50_geo.py', 'c3': 'configs/c3_deeplabv3_r101.py',
+        'c4': 'configs/c4_msa_hrnet.py', 'c5': 'configs/c5_hardnet_disc.py'}
 
 
 def train_loop(name, path, dev, threshold, calibrate, n_warm=4, n_timed=10):
