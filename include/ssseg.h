@@ -236,6 +236,44 @@ int ssseg_lovasz_bwd_from_fwd(const float* logits, const float* target, int64_t 
                               const float* gout, float* grad_out, const void* ws, size_t ws_bytes,
                               ssseg_stream_t stream);
 
+/* General Lovász losses (lovasz.py:79-127, 155-220) on the device, no host synchronisation.
+ * x [B,C,HW] f32: class probabilities (SSSEG_LOVASZ_PROBAS; C == 1 is the reference's sigmoid case, channel 0 is the
+ * prediction of the one selected class), logits with the softmax over C fused (SSSEG_LOVASZ_SOFTMAX, C >= 2), or
+ * one-channel logits of the binary hinge (SSSEG_LOVASZ_HINGE: C == 1, classes = {1}, labels 0 / 1).
+ * labels [B,HW]: int64, uint8 or f32 values read in place, or SSSEG_LOVASZ_LABEL_DENSE: a [B,C,HW] f32 target whose
+ * argmax over C (first maximum) is the label.  has_ignore: pixels labelled `ignore` are removed.  Any other label that
+ * is not a selected class is background for all of them.
+ * classes: HOST array of nsel class ids (1 <= nsel <= 64; C > 1: each in [0, C); C == 1: nsel == 1), read during the
+ * call only.  present != 0: of these, only the classes with a foreground pixel in the group count ('present').
+ * per_image: one group per image (G = B, L = HW), else one group (G = 1, L = B*HW).
+ * Per (group, class): e = |fg - p| (hinge: 1 - x*(2*fg - 1)) sorted descending and stable over the valid pixels,
+ * Lovász gradient in fp32 (lovasz_grad lovasz.py:19-31), dot in fp64 (hinge: with relu(e)).  loss_out[0] = fp32 mean
+ * over groups of the fp32 mean over the counted classes.  A group with no valid pixel, or with no counted class,
+ * contributes 0 and still counts in the mean over groups (where the reference returns an empty tensor or raises).
+ * Bounds: 1 <= C <= 64, L <= 2^24, G*nsel <= 65535, else SSSEG_EINVAL (workspace_bytes returns 0).
+ * grad_out [B,C,HW] = gout[0] (1 if NULL) * d loss / d x; ignored pixels, channels of no selected class (PROBAS) and
+ * classes not counted get exact zeros.  _bwd sorts again; _bwd_from_fwd is the backward of the immediately preceding
+ * _fwd with the same arguments and workspace (kept unchanged in between) and only scatters: bitwise the same. */
+#define SSSEG_LOVASZ_PROBAS 0
+#define SSSEG_LOVASZ_SOFTMAX 1
+#define SSSEG_LOVASZ_HINGE 2
+#define SSSEG_LOVASZ_LABEL_I64 0
+#define SSSEG_LOVASZ_LABEL_U8 1
+#define SSSEG_LOVASZ_LABEL_F32 2
+#define SSSEG_LOVASZ_LABEL_DENSE 3
+size_t ssseg_lovasz_gen_workspace_bytes(int64_t B, int64_t C, int64_t HW, int per_image, int64_t nsel);
+int ssseg_lovasz_gen_fwd(const float* x, const void* labels, int label_kind, int64_t B, int64_t C, int64_t HW,
+                         int mode, int per_image, int present, const int64_t* classes, int64_t nsel, int has_ignore,
+                         int64_t ignore, float* loss_out, void* ws, size_t ws_bytes, ssseg_stream_t stream);
+int ssseg_lovasz_gen_bwd(const float* x, const void* labels, int label_kind, int64_t B, int64_t C, int64_t HW,
+                         int mode, int per_image, int present, const int64_t* classes, int64_t nsel, int has_ignore,
+                         int64_t ignore, const float* gout, float* grad_out, void* ws, size_t ws_bytes,
+                         ssseg_stream_t stream);
+int ssseg_lovasz_gen_bwd_from_fwd(const float* x, const void* labels, int label_kind, int64_t B, int64_t C, int64_t HW,
+                                  int mode, int per_image, int present, const int64_t* classes, int64_t nsel,
+                                  int has_ignore, int64_t ignore, const float* gout, float* grad_out, const void* ws,
+                                  size_t ws_bytes, ssseg_stream_t stream);
+
 /* RMILoss, sigmoid form (losses.RMILoss.forward -> forward_sigmoid -> rmi_lower_bound, losses.py:480-592; the
  * default-config loss, configs/default_config.py:147).  logits, target [N,C,H,W] f32 contiguous.
  * pool (k, s, pad): avg_pool2d(k, s, pad, count_include_pad) of losses.py:534-538 (k == s, pad = k/2; (1,1,0) for

@@ -10,6 +10,8 @@
   get_dims_with_exclusion                 losses.py:213-218
   dice_loss, log_dice_loss                losses.py:221-236
   binary_lovasz_loss_with_logits          losses.py:239-250
+  LovaszSoftmaxLossWithLogits             lovasz.py:155-201 on logits, softmax fused (any C <= 64, classes, ignore)
+  LovaszHingeLossWithLogits               lovasz.py:79-112 on one-channel logits
   binary_entropy_loss, entropy_loss       losses.py:253-264
   smooth_labels                           losses.py:267-268
   RMILoss                                 losses.py:271-592 (the default-config loss, configs/default_config.py:147;
@@ -162,6 +164,48 @@ def smooth_labels(target, alpha=0.1):
 def binary_lovasz_loss_with_logits(input, target):
     """losses.py:239-250: per-image binary Lovász-softmax on raw logits (class 1), sum(loss*valid)/(sum valid + 0.001)."""
     return ops.lovasz_binary(input, target)
+
+
+class LovaszSoftmaxLossWithLogits(nn.Module):
+    """Multi-class Lovász-softmax (lovasz.lovasz_softmax) on raw logits [B, C, H, W] against a one-hot or soft target
+    of the same shape: the label of a pixel is the argmax of its target (as in binary_lovasz_loss_with_logits), read
+    inside the kernels; the softmax over C is fused into them.  A target [B, H, W] is taken as the label map itself
+    (int64 or uint8, read in place).  classes: 'present', 'all' or a list of class ids; ignore: the label value of void
+    pixels (only a label map can hold the default 255: an argmax over C <= 64 channels never reaches it)."""
+
+    def __init__(self, classes='present', per_image=False, ignore=255):
+        super().__init__()
+        if isinstance(classes, str) and classes not in ('all', 'present'):
+            raise ValueError(f"classes must be 'all', 'present' or a list of class ids, got {classes!r}")
+        self.classes = classes
+        self.per_image = per_image
+        self.ignore = ignore
+
+    def forward(self, input, target):
+        if input.dim() != 4 or input.shape[1] < 2:
+            raise ValueError(f'LovaszSoftmaxLossWithLogits: expected logits [B, C >= 2, H, W], got {tuple(input.shape)}')
+        if isinstance(self.classes, str):
+            ids, present = list(range(input.shape[1])), self.classes == 'present'
+        else:
+            ids, present = list(self.classes), False
+        return ops.lovasz_general(input, target, N.LOVASZ_SOFTMAX, ids, self.per_image, self.ignore, present,
+                                  dense_target=target.dim() == input.dim())
+
+
+class LovaszHingeLossWithLogits(nn.Module):
+    """Binary Lovász hinge (lovasz.lovasz_hinge) on one-channel logits [B, 1, H, W] against a 0 / 1 mask of the same
+    number of pixels ([B, 1, H, W] or [B, H, W]; float masks are read in place); ignore: the mask value of void
+    pixels, None for no void."""
+
+    def __init__(self, per_image=True, ignore=None):
+        super().__init__()
+        self.per_image = per_image
+        self.ignore = ignore
+
+    def forward(self, input, target):
+        if input.dim() != 4 or input.shape[1] != 1:
+            raise ValueError(f'LovaszHingeLossWithLogits: expected logits [B, 1, H, W], got {tuple(input.shape)}')
+        return ops.lovasz_general(input, target, N.LOVASZ_HINGE, [1], self.per_image, self.ignore)
 
 
 class RMILoss(nn.Module):

@@ -69,6 +69,12 @@ SIGS = {
     'ssseg_lovasz_fwd': (i32, [vp, vp, i64, i64, i64, vp, vp, sz, vp]),
     'ssseg_lovasz_bwd': (i32, [vp, vp, i64, i64, i64, vp, vp, vp, sz, vp]),
     'ssseg_lovasz_bwd_from_fwd': (i32, [vp, vp, i64, i64, i64, vp, vp, vp, sz, vp]),
+    'ssseg_lovasz_gen_workspace_bytes': (sz, [i64, i64, i64, i32, i64]),
+    'ssseg_lovasz_gen_fwd': (i32, [vp, vp, i32, i64, i64, i64, i32, i32, i32, I64P, i64, i32, i64, vp, vp, sz, vp]),
+    'ssseg_lovasz_gen_bwd': (i32, [vp, vp, i32, i64, i64, i64, i32, i32, i32, I64P, i64, i32, i64, vp, vp, vp, sz,
+                                   vp]),
+    'ssseg_lovasz_gen_bwd_from_fwd': (i32, [vp, vp, i32, i64, i64, i64, i32, i32, i32, I64P, i64, i32, i64, vp, vp,
+                                            vp, sz, vp]),
     'ssseg_rmi_workspace_bytes': (sz, [i64] * 9),
     'ssseg_rmi_fwd': (i32, [vp, vp] + [i64] * 9 + [i32, vp, vp, sz, vp]),
     'ssseg_rmi_bwd': (i32, [vp] + [i64] * 9 + [vp, vp, vp, sz, vp]),
@@ -223,6 +229,8 @@ OPT_ADAM, OPT_ADAMOD, OPT_DIFFGRAD, OPT_DIFFMOD, OPT_RANGER = range(5)
 OPT_STATE_DOUBLES = 8
 RED_NONE, RED_MEAN, RED_SUM = 0, 1, 2
 LOSS_REDUCE, LOSS_OHEM, LOSS_NFL, LOSS_DICE_LOGITS, LOSS_DICE_PROB = 0, 1, 2, 3, 4
+LOVASZ_PROBAS, LOVASZ_SOFTMAX, LOVASZ_HINGE = 0, 1, 2                        # SSSEG_LOVASZ_* (include/ssseg.h)
+LOVASZ_LABEL_I64, LOVASZ_LABEL_U8, LOVASZ_LABEL_F32, LOVASZ_LABEL_DENSE = 0, 1, 2, 3
 
 
 class VCat(ctypes.Structure):

@@ -410,10 +410,95 @@ class _Lovasz(torch.autograd.Function):
 
 
 def lovasz_binary(logits, target, valid_weighted=True):
-    """binary_lovasz_loss_with_logits (losses.py:239-250) on the device."""
+    """binary_lovasz_loss_with_logits (losses.py:239-250) on the device.  valid_weighted=False is the plain
+    lovasz_softmax(classes=[1], per_image=True) of its building block (lovasz.py:155-170): the mean over all images,
+    through the general kernels with the dense target's argmax as the label."""
     if not valid_weighted:
-        raise NotImplementedError('lovasz_softmax without the valid-sample weighting')
+        return lovasz_general(logits, target, N.LOVASZ_PROBAS, [1], per_image=True, dense_target=True)
     return _Lovasz.apply(logits, target)
+
+
+# ------------------------------------------------------------------------------------------------
+# General Lovász losses (lovasz.py:79-127, 155-220): csrc/lovasz.hip, ssseg_lovasz_gen_*
+# ------------------------------------------------------------------------------------------------
+class _LovaszGen(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, labels, cfg):
+        kind, mode, per_image, present, classes, ignore = cfg
+        B, C = x.shape[:2]
+        HW = x[0, 0].numel()
+        sel = (ctypes.c_int64 * len(classes))(*classes)
+        args = (kind, B, C, HW, mode, int(per_image), int(present), sel, len(classes), int(ignore is not None),
+                int(ignore) if ignore is not None else 0)
+        nb = N.lib().ssseg_lovasz_gen_workspace_bytes(B, C, HW, int(per_image), len(classes))
+        if nb == 0:
+            raise ValueError(f'lovasz: input {tuple(x.shape)} with {len(classes)} classes, per_image={per_image} is '
+                             'outside the kernels\' bounds (1 <= C <= 64, at most 2^24 pixels per group, '
+                             'groups * classes <= 65535)')
+        out = torch.empty((), device=x.device, dtype=torch.float32)
+        ws = N.workspace(nb, x.device)
+        N.call('ssseg_lovasz_gen_fwd', N.dev_ptr(x, 'input'), N.dev_ptr(labels, 'labels'), *args, N.dev_ptr(out),
+               N.dev_ptr(ws), nb, N.stream())
+        ctx.save_for_backward(x, labels)
+        ctx.args, ctx.ws, ctx.nb = args, ws, nb   # the forward's per-pixel weights and class scales: no second sort
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, labels = ctx.saved_tensors
+        gx = torch.empty_like(x)
+        g = _c(g.float())
+        N.call('ssseg_lovasz_gen_bwd_from_fwd', N.dev_ptr(x), N.dev_ptr(labels), *ctx.args, N.dev_ptr(g),
+               N.dev_ptr(gx), N.dev_ptr(ctx.ws), ctx.nb, N.stream())
+        # (ctx.ws stays for the lifetime of ctx: a second backward through a retained graph reads it again)
+        return gx, None, None
+
+
+def lovasz_label_kind(labels):
+    """(labels as the kernels read them in place, SSSEG_LOVASZ_LABEL_* code); other integer types become int64"""
+    if labels.dtype == torch.uint8:
+        return _c(labels), N.LOVASZ_LABEL_U8
+    if labels.dtype == torch.float32:
+        return _c(labels), N.LOVASZ_LABEL_F32
+    if labels.dtype.is_floating_point:
+        return _c(labels.float()), N.LOVASZ_LABEL_F32
+    return _c(labels.long()), N.LOVASZ_LABEL_I64
+
+
+def lovasz_general(x, labels, mode, classes, per_image=False, ignore=None, present=False, dense_target=False):
+    """The Lovász family on the device.  x [B, C, ...] f32: probabilities (LOVASZ_PROBAS), logits with the softmax
+    fused (LOVASZ_SOFTMAX) or one-channel hinge logits (LOVASZ_HINGE).  labels [B, ...] (int64 / uint8 / float
+    values), or with dense_target a [B, C, ...] target whose argmax is the label.  classes: list of class ids;
+    present: count only those with a foreground pixel in the group.  Returns the scalar loss (differentiable in x)."""
+    if x.dim() < 3:
+        raise ValueError(f'lovasz: expected input [B, C, ...], got {tuple(x.shape)}')
+    x = _c(x.float())
+    B, C = x.shape[:2]
+    HW = x[0, 0].numel()
+    classes = [int(c) for c in classes]
+    if not classes:
+        raise ValueError('lovasz: `classes` is empty')
+    if not 1 <= C <= 64:
+        raise ValueError(f'lovasz: {C} channels (the kernels cover 1 <= C <= 64)')
+    if len(classes) > 64:
+        raise ValueError(f'lovasz: {len(classes)} classes selected (the kernels cover at most 64)')
+    if C == 1 and len(classes) != 1:
+        raise ValueError('Sigmoid output possible only with 1 class')
+    if C > 1 and not all(0 <= c < C for c in classes):
+        raise ValueError(f'lovasz: classes {classes} outside [0, {C})')
+    if dense_target:
+        if tuple(labels.shape) != tuple(x.shape):
+            raise ValueError(f'lovasz: input {tuple(x.shape)} and dense target {tuple(labels.shape)} must have the '
+                             'same shape')
+        if C < 2:
+            raise ValueError('lovasz: a dense target needs at least two channels')
+        labels, kind = _c(labels.float()), N.LOVASZ_LABEL_DENSE
+    else:
+        if labels.numel() != B * HW:
+            raise ValueError(f'lovasz: labels {tuple(labels.shape)} do not hold one label per pixel of '
+                             f'{tuple(x.shape)}')
+        labels, kind = lovasz_label_kind(labels)
+    return _LovaszGen.apply(x, labels, (kind, int(mode), bool(per_image), bool(present), tuple(classes), ignore))
 
 
 # ------------------------------------------------------------------------------------------------
