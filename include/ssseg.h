@@ -216,6 +216,16 @@ int ssseg_consistency_w_fwd(const float* s, const float* t, const float* w, int6
                             float thr, float* out3, void* ws, size_t ws_bytes, ssseg_stream_t stream);
 int ssseg_consistency_w_bwd(const float* s, const float* t, const float* w, int64_t B, int64_t C, int64_t HW,
                             float thr, const float* out3, const float* gout, float* gs, ssseg_stream_t stream);
+/* The consistency loss over mutually exclusive classes (csrc/multiclass.hip; train.py:97-108 with the softmax lines
+ * :97,:99 in place of the sigmoid ones).  s, t [B,C,HW] f32 contiguous, 1 <= C <= 64 (SSSEG_EINVAL otherwise);
+ * w [B,HW] f32 per-pixel weight or NULL (NULL gives the bits of w == 1).  ps = softmax_c(s), pt = softmax_c(t) with
+ * the per-pixel maximum subtracted, d = ps - pt, cm = [max_c pt > thr] * w:
+ * out[0] = sum_pix (sum_c d_c^2) cm / sum(cm) (NaN on 0/0);  out[1] = sum(cm) / (B HW);  out[2] = sum(cm).
+ * gs_c = 2 gout[0] cm / out3[2] * ps_c (d_c - sum_k d_k ps_k).  Workspace: ssseg_reduce_workspace_bytes(B*HW). */
+int ssseg_consistency_sm_fwd(const float* s, const float* t, const float* w, int64_t B, int64_t C, int64_t HW,
+                             float thr, float* out3, void* ws, size_t ws_bytes, ssseg_stream_t stream);
+int ssseg_consistency_sm_bwd(const float* s, const float* t, const float* w, int64_t B, int64_t C, int64_t HW,
+                             float thr, const float* out3, const float* gout, float* gs, ssseg_stream_t stream);
 
 /* Binary Lovász (losses.binary_lovasz_loss_with_logits losses.py:239-250 -> lovasz_softmax
  * lovasz.py:155-201 with classes=[1], per_image=True).  logits, target [B,C,HW] f32, 1 <= B <= 4096.
@@ -948,6 +958,27 @@ int ssseg_seg_metrics(const float* logits, const int64_t* l_strides4_host, int64
 /* InferenceWrapper head (models/inference_wrapper.py:17-24): logits contiguous [B][2][HW] f32 ->
  * prob = sigmoid(logits), onehot = one_hot(argmax_c logits) (first max, NaN is max), both [B][2][HW] f32. */
 int ssseg_prob_onehot(const float* logits, int64_t B, int64_t HW, float* prob, float* onehot, ssseg_stream_t stream);
+
+/* The C-class forms of the two entry points above (csrc/multiclass.hip), 1 <= C <= 64, B <= 65535.
+ * Metrics: logits [B][C][h][w] f32, any strides (4 host element strides); pred = argmax_c (first max, NaN is max),
+ * nearest-resized to HxW.  target_is_labels == 0: target is a dense mask [B][C][H][W] f32 (4 host strides),
+ * label = argmax_c mask (first max), t_c = mask_c > 0.5.  target_is_labels != 0: target is a label map [B][H][W]
+ * int64 (3 host strides), t_c = [label == c]; with ignore_on != 0 the pixels whose label == ignore are left out of
+ * every count, and so is any label outside [0, C).
+ * conf [C][C] u64 (overwritten): the batch's confusion matrix, rows label, columns prediction.
+ * total [C][C] u64 (nullable): running matrix the batch is added to; the IoUs then come from it.
+ * dice [B][2] u64 (overwritten): I_b = sum_{c>=1} sum pred_c t_c, card_b = sum_{c>=1} sum (pred_c + t_c).
+ * out [2 + C]: out[0] = mean_b (2 I_b + 1)/(card_b + 1) (metrics.dice_metric on channels 1.., metrics.py:1-7);
+ * out[1] = mean_c IoU_c (a fraction);  out[2 + c] = 100 IoU_c, IoU_c = inter / union, 1 where union == 0
+ * (lovasz.iou lovasz.py:54-73, per_image=False).  All counting is integer: exact and order-independent. */
+int ssseg_seg_metrics_mc(const float* logits, const int64_t* l_strides4_host, int64_t h, int64_t w, const void* target,
+                         const int64_t* t_strides_host, int target_is_labels, int ignore_on, int64_t ignore,
+                         int64_t B, int64_t C, int64_t H, int64_t W, unsigned long long* conf,
+                         unsigned long long* total, unsigned long long* dice, float* out, ssseg_stream_t stream);
+/* logits contiguous [B][C][HW] f32 -> prob = sigmoid(logits) (activation 0, the reference) or softmax_c(logits)
+ * (activation 1), onehot = one_hot(argmax_c logits) (first max, NaN is max), both [B][C][HW] f32. */
+int ssseg_prob_onehot_mc(const float* logits, int64_t B, int64_t C, int64_t HW, int activation, float* prob,
+                         float* onehot, ssseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Collectives: the data-parallel gradient all-reduce and the SyncBN sums

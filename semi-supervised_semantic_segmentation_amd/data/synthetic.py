@@ -1,6 +1,8 @@
 """Synthetic labeled / unlabeled segmentation datasets for the BASELINE configs: images
 U[0,1) and 2-channel one-hot masks of smoothed-noise blobs.  The reference's SkinSegDataset needs
-cv2 + albumentations (absent here)."""
+cv2 + albumentations (absent here).  num_classes > 2 gives C-channel one-hot masks: the same
+smoothed field cut at C - 1 quantiles into nested level sets (background fg_fraction-complement, the rest shared
+equally by classes 1 .. C-1)."""
 import math
 
 import torch
@@ -8,12 +10,16 @@ import torch.nn.functional as F
 
 
 class SyntheticSegDataset(torch.utils.data.Dataset):
-    def __init__(self, length=64, size=512, seed=0, with_masks=True, blob_sigma=16.0, fg_fraction=0.4, uint8=False):
+    def __init__(self, length=64, size=512, seed=0, with_masks=True, blob_sigma=16.0, fg_fraction=0.4, uint8=False,
+                 num_classes=2):
         self.length, self.size, self.seed = length, size, seed
         self.with_masks, self.sigma, self.fg = with_masks, blob_sigma, fg_fraction
         # uint8: the image as the reference's host loader leaves it before ToFloat (LongestMaxSize + PadIfNeeded
         # output, data/dataset.py:70-72), for the device augmentation pipeline (data.device_augment)
         self.uint8 = uint8
+        if int(num_classes) < 2:
+            raise ValueError(f'SyntheticSegDataset: num_classes must be at least 2, got {num_classes}')
+        self.num_classes = int(num_classes)
 
     def __len__(self):
         return self.length
@@ -25,8 +31,15 @@ class SyntheticSegDataset(torch.utils.data.Dataset):
         w = (w / w.sum()).view(1, 1, k, 1)
         n = torch.randn(1, 1, self.size, self.size, generator=g)
         f = F.conv2d(F.conv2d(n, w, padding=(k // 2, 0)), w.transpose(2, 3), padding=(0, k // 2))
-        thr = torch.quantile(f.flatten(), 1 - self.fg)
-        return (f > thr).float()[0]
+        if self.num_classes == 2:
+            thr = torch.quantile(f.flatten(), 1 - self.fg)
+            return (f > thr).float()[0]
+        # C classes: level k (1 <= k < C) starts at the quantile 1 - fg * (C - k) / (C - 1) of the field
+        C = self.num_classes
+        q = torch.tensor([1 - self.fg * (C - k) / (C - 1) for k in range(1, C)], dtype=torch.float32)
+        thr = torch.quantile(f.flatten(), q)
+        label = (f[0] > thr.view(-1, 1, 1)).sum(0)                       # [size, size] in [0, C)
+        return F.one_hot(label, C).permute(2, 0, 1).float()
 
     def __getitem__(self, i):
         g = torch.Generator().manual_seed(self.seed * 1_000_003 + i)
@@ -35,5 +48,5 @@ class SyntheticSegDataset(torch.utils.data.Dataset):
             out['image'] = (out['image'] * 255).round().to(torch.uint8)
         if self.with_masks:
             fg = self._blobs(g)
-            out['semantic_mask'] = torch.cat([1 - fg, fg], 0)
+            out['semantic_mask'] = torch.cat([1 - fg, fg], 0) if self.num_classes == 2 else fg
         return out

@@ -65,6 +65,8 @@ SIGS = {
     'ssseg_consistency_bwd': (i32, [vp, vp, i64, i64, i64, f32, vp, vp, vp, vp]),
     'ssseg_consistency_w_fwd': (i32, [vp, vp, vp, i64, i64, i64, f32, vp, vp, sz, vp]),
     'ssseg_consistency_w_bwd': (i32, [vp, vp, vp, i64, i64, i64, f32, vp, vp, vp, vp]),
+    'ssseg_consistency_sm_fwd': (i32, [vp, vp, vp, i64, i64, i64, f32, vp, vp, sz, vp]),
+    'ssseg_consistency_sm_bwd': (i32, [vp, vp, vp, i64, i64, i64, f32, vp, vp, vp, vp]),
     'ssseg_lovasz_workspace_bytes': (sz, [i64, i64]),
     'ssseg_lovasz_fwd': (i32, [vp, vp, i64, i64, i64, vp, vp, sz, vp]),
     'ssseg_lovasz_bwd': (i32, [vp, vp, i64, i64, i64, vp, vp, vp, sz, vp]),
@@ -101,6 +103,9 @@ SIGS = {
     'ssseg_smooth_labels': (i32, [vp, vp, i64, f32, f32, vp]),
     'ssseg_prob_onehot': (i32, [vp, i64, i64, vp, vp, vp]),
     'ssseg_seg_metrics': (i32, [vp, I64P, i64, i64, vp, I64P, i64, i64, i64, vp, vp, vp, vp]),
+    'ssseg_seg_metrics_mc': (i32, [vp, I64P, i64, i64, vp, I64P, i32, i32, i64, i64, i64, i64, i64, vp, vp, vp, vp,
+                                   vp]),
+    'ssseg_prob_onehot_mc': (i32, [vp, i64, i64, i64, i32, vp, vp, vp]),
     'ssseg_ema_update': (i32, [vp, vp, i64, f64, vp]),
     'ssseg_scale_f32': (i32, [vp, i64, f32, vp]),
     'ssseg_axpby': (i32, [vp, f32, vp, f32, vp, i64, vp]),

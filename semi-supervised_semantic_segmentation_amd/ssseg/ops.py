@@ -335,6 +335,64 @@ def consistency_loss_weighted(student_logits, teacher_logits, w, thr):
     return _Consistency.apply(student_logits, teacher_logits, thr, w)
 
 
+def _device_checked(name, **tensors):
+    for n, t in tensors.items():
+        if t is not None and not t.is_cuda:
+            raise ValueError(f'{name}: {n} must be a HIP device tensor (no CPU fallback), got {t.device}')
+
+
+class _ConsistencySoftmax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, s, t, thr, w):
+        s, t = _c(s.float()), _c(t.float())
+        B, C = s.shape[:2]
+        HW = s[0, 0].numel()
+        out = torch.empty(3, device=s.device, dtype=torch.float32)
+        nb = N.lib().ssseg_reduce_workspace_bytes(B * HW)
+        ws = N.workspace(nb, s.device)
+        if w is not None:
+            w = _c(w.float())
+        N.call('ssseg_consistency_sm_fwd', N.dev_ptr(s, 'student'), N.dev_ptr(t, 'teacher'), N.dev_ptr(w, 'w'), B, C,
+               HW, float(thr), N.dev_ptr(out), N.dev_ptr(ws), nb, N.stream())
+        if w is None:
+            ctx.save_for_backward(s, t, out)
+        else:
+            ctx.save_for_backward(s, t, out, w)
+        ctx.meta = (B, C, HW, float(thr))
+        loss, cm = out[0], out[1]
+        ctx.mark_non_differentiable(cm)
+        ctx.set_materialize_grads(False)   # no zero-filled gradient for the cm output (a framework fill kernel)
+        return loss, cm
+
+    @staticmethod
+    def backward(ctx, g_loss, g_cm):
+        s, t, out = ctx.saved_tensors[:3]
+        w = ctx.saved_tensors[3] if len(ctx.saved_tensors) > 3 else None
+        B, C, HW, thr = ctx.meta
+        gs = torch.empty_like(s)
+        g = _c(g_loss.float())
+        N.call('ssseg_consistency_sm_bwd', N.dev_ptr(s), N.dev_ptr(t), N.dev_ptr(w), B, C, HW, thr, N.dev_ptr(out),
+               N.dev_ptr(g), N.dev_ptr(gs), N.stream())
+        return gs, None, None, None
+
+
+def consistency_loss_softmax(student_logits, teacher_logits, thr, w=None):
+    """The consistency loss over mutually exclusive classes: train.py:97-108 with the softmax lines (:97, :99) in
+    place of the sigmoid ones.  [B,C,H,W] logits, 1 <= C <= 64; w [B,H,W] (optional, a constant) multiplies the
+    confidence modulator like consistency_loss_weighted.  Returns (loss, sum(cm w) / npix); the loss is NaN when no
+    weighted pixel is confident."""
+    s, t = student_logits, teacher_logits
+    if s.dim() < 3 or tuple(s.shape) != tuple(t.shape):
+        raise ValueError(f'consistency_loss_softmax: student and teacher logits must have one shape [B,C,H,W], got '
+                         f'{tuple(s.shape)} and {tuple(t.shape)}')
+    if s.shape[1] > 64:
+        raise ValueError(f'consistency_loss_softmax: {s.shape[1]} channels (at most 64 are supported)')
+    if w is not None and w.numel() != s.shape[0] * s[0, 0].numel():
+        raise ValueError('consistency_loss_softmax: w must hold one weight per pixel, [B, H, W]')
+    _device_checked('consistency_loss_softmax', student=s, teacher=t, w=w)
+    return _ConsistencySoftmax.apply(s, t, thr, w)
+
+
 # ------------------------------------------------------------------------------------------------
 # EMA / optimiser over flat arenas
 # ------------------------------------------------------------------------------------------------
@@ -915,12 +973,75 @@ class SegMetrics:
         return out
 
 
-def prob_onehot(logits):
-    """sigmoid probabilities + one-hot argmax mask of binary logits [B,2,H,W] (inference_wrapper.py:17-24)."""
-    if logits.dim() != 4 or logits.shape[1] != 2:
-        raise ValueError('prob_onehot: binary [B,2,H,W] logits expected')
+class SegMetricsMC:
+    """SegMetrics for num_classes mutually exclusive classes (1 <= C <= 64): train.py:171-175 with num_classes = C
+    (Dice of the nearest-resized argmax one-hot over channels 1..) and the confusion matrix of lovasz.iou
+    (lovasz.py:54-73, per_image=False) in one pass per batch.  `update(logits, target)` takes [B,C,h,w] logits and
+    either a dense [B,C,H,W] mask or a [B,H,W] int64 label map (pixels labelled `ignore` are left out of every count)
+    and returns the device vector [dice_mean, mean IoU (a fraction), 100*IoU_0, ..., 100*IoU_{C-1}]; the IoUs are
+    over every batch seen so far.  .total [C,C] is the running confusion matrix (rows label, columns prediction),
+    .counts the last batch's, .dice its per-image [B,2] Dice numerators and denominators."""
+
+    def __init__(self, device, num_classes, ignore=None):
+        num_classes = int(num_classes)
+        if not 1 <= num_classes <= 64:
+            raise ValueError(f'SegMetricsMC: {num_classes} channels (1 to 64 are supported)')
+        self.device = torch.device(device)
+        self.num_classes = num_classes
+        self.ignore = None if ignore is None else int(ignore)
+        self.total = torch.zeros(num_classes, num_classes, dtype=torch.int64, device=self.device)
+        self.counts = self.dice = None
+
+    def update(self, logits, target):
+        C = self.num_classes
+        if logits.dim() != 4 or logits.shape[1] != C:
+            raise ValueError(f'SegMetricsMC: [B,{C},h,w] logits expected, got {tuple(logits.shape)}')
+        labels = target.dim() == 3
+        if labels:
+            if target.dtype != torch.int64:
+                raise ValueError('SegMetricsMC: a [B,H,W] label map must be int64')
+        elif target.dim() != 4 or target.shape[1] != C:
+            raise ValueError(f'SegMetricsMC: a [B,{C},H,W] mask or a [B,H,W] int64 label map expected, got '
+                             f'{tuple(target.shape)}')
+        if logits.shape[0] != target.shape[0]:
+            raise ValueError('SegMetricsMC: batch size mismatch')
+        _device_checked('SegMetricsMC', logits=logits, target=target)
+        logits = logits if logits.dtype == torch.float32 else logits.float()
+        if not labels:
+            target = target if target.dtype == torch.float32 else target.float()
+        B, _, h, w = logits.shape
+        H, W = target.shape[-2:]
+        counts = torch.empty(C, C, dtype=torch.int64, device=logits.device)
+        dice = torch.empty(B, 2, dtype=torch.int64, device=logits.device)
+        out = torch.empty(2 + C, dtype=torch.float32, device=logits.device)
+        tstr = (ctypes.c_int64 * 4)(*(tuple(target.stride()) + (0,) * (4 - target.dim())))
+        N.call('ssseg_seg_metrics_mc', N.dev_ptr(logits, 'logits'), N.strides4(logits), h, w,
+               N.dev_ptr(target, 'target'), tstr, int(labels), int(self.ignore is not None),
+               self.ignore if self.ignore is not None else 0, B, C, H, W, N.dev_ptr(counts), N.dev_ptr(self.total),
+               N.dev_ptr(dice), N.dev_ptr(out), N.stream())
+        self.counts, self.dice = counts, dice
+        return out
+
+
+_ACTIVATIONS = {'sigmoid': 0, 'softmax': 1}
+
+
+def prob_onehot(logits, activation='sigmoid'):
+    """Probabilities + one-hot argmax mask of [B,C,H,W] logits (inference_wrapper.py:17-24): sigmoid per channel (the
+    reference) or softmax over the channels.  Binary logits with sigmoid take the two-class kernel."""
+    if activation not in _ACTIVATIONS:
+        raise ValueError(f"prob_onehot: activation must be 'sigmoid' or 'softmax', got {activation!r}")
+    if logits.dim() != 4:
+        raise ValueError('prob_onehot: [B,C,H,W] logits expected')
+    if logits.shape[1] > 64:
+        raise ValueError(f'prob_onehot: {logits.shape[1]} channels (at most 64 are supported)')
     x = _c(logits.float())
     prob, onehot = torch.empty_like(x), torch.empty_like(x)
-    B, _, H, W = x.shape
-    N.call('ssseg_prob_onehot', N.dev_ptr(x, 'logits'), B, H * W, N.dev_ptr(prob), N.dev_ptr(onehot), N.stream())
+    B, C, H, W = x.shape
+    if C == 2 and activation == 'sigmoid':
+        N.call('ssseg_prob_onehot', N.dev_ptr(x, 'logits'), B, H * W, N.dev_ptr(prob), N.dev_ptr(onehot), N.stream())
+    else:
+        _device_checked('prob_onehot', logits=x)
+        N.call('ssseg_prob_onehot_mc', N.dev_ptr(x, 'logits'), B, C, H * W, _ACTIVATIONS[activation], N.dev_ptr(prob),
+               N.dev_ptr(onehot), N.stream())
     return prob, onehot

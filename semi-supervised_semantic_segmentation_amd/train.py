@@ -160,6 +160,14 @@ def _consistency_augmentation(tc):
     return aug
 
 
+def _consistency_activation(tc):
+    """config['train']['consistency_activation']: 'sigmoid' (the reference, and the default) or 'softmax'."""
+    activation = tc.get('consistency_activation', 'sigmoid')
+    if activation not in ('sigmoid', 'softmax'):
+        raise ValueError(f"consistency_activation must be 'sigmoid' or 'softmax', got {activation!r}")
+    return activation
+
+
 def _consistency_forward(model, targets, tc, epoch):
     """train.py:87-112: the student's eval-mode forward on the mixed images (with grad), resized, and the weighted
     consistency loss.  Returns (unsup_loss, cm_mean)."""
@@ -173,8 +181,15 @@ def _consistency_forward(model, targets, tc, epoch):
         student_pred = model(view)[-1][-1]
     model.train()
     student_pred = ops.interpolate_bilinear(student_pred, mixed_images.shape[2:4], align_corners=False)
+    activation = _consistency_activation(tc)
     if aug is not None:
         student_pred = aug.reverse([student_pred])[0]
+    if activation == 'softmax':
+        # mutually exclusive classes (the reference's commented alternative, train.py:97,99): one softmax over the
+        # channels, so that max_c p is a class confidence and confidence_threshold means what it says at any C
+        consistency, cm_mean = ops.consistency_loss_softmax(student_pred, mixed_ema_pred, tc['confidence_threshold'],
+                                                            aug.valid if aug is not None else None)
+    elif aug is not None:
         consistency, cm_mean = ops.consistency_loss_weighted(student_pred, mixed_ema_pred, aug.valid,
                                                              tc['confidence_threshold'])
     else:
@@ -318,7 +333,8 @@ def train_step(model, ema_model, optimizer, image, mask, unsup_a, unsup_b, epoch
 # the benchmark: C5 (HarDNet + discriminator, ~660 small launches) 63.6 -> 33.5 ms/step, C4 213 -> 195 ms.  A replay
 # repeats the Python decisions of its capture, so the graph is keyed on every one of them: the optimizer step taken
 # or skipped (train.py:121, step % virtual_batch_size_multiplier), the epoch gate of the consistency weight
-# (train.py:112), every learning rate, the input geometry and compute dtype -- a new key captures a new graph (the two
+# (train.py:112), the consistency activation, every learning rate, the input geometry and compute dtype -- a new key
+# captures a new graph (the two
 # most recent are kept).  Not captured (eager steps instead): CowMix drawn from the CPU generator (parity mode), a
 # consistency augmentation whose parameters come from the host (source='cpu' or set_params), steps
 # with collectives on torch.distributed (gloo, or SSSEG_COMM=c10d: the native RCCL communicator's steps ARE captured),
@@ -363,7 +379,8 @@ def _graph_key(model, ema_model, optimizer, image, mask, unsup_a, unsup_b, epoch
         return None
     lrs = tuple(float(g['lr']) for o in opts for g in o.param_groups)
     shapes = tuple((tuple(t.shape), t.dtype) if t is not None else None for t in (image, mask, unsup_a, unsup_b))
-    return step_key + (id(optimizer), opt_step, float(epoch > 25), lrs, shapes, id(config))
+    return step_key + (id(optimizer), opt_step, float(epoch > 25), lrs, shapes, id(config),
+                       _consistency_activation(tc))
 
 
 def _graph_step(key, model, ema_model, optimizer, image, mask, unsup_a, unsup_b, epoch, step, config):
@@ -482,9 +499,15 @@ def train(model, ema_model, optimizer, dataloader, unsupervised_dataloader, epoc
         summary_writer.add_scalar('train_confidence_modulator', meters['cm'].average(), global_step)
 
 
+# the last validate()'s mIoU (percent) and, for a multi-class set, the per-class IoUs: validate() returns the
+# reference's (avg_loss, avg_metric) pair only
+_VALIDATE = {'miou': None, 'class_ious': None}
+
+
 def validate(model, dataloader, epoch, initial_step, summary_writer, config, device):
     """train.py:150-195: Dice on the nearest-resized argmax one-hot (the reference metric) plus mIoU over the
-    whole validation set (lovasz.iou, lovasz.py:54-73) from the same device pass (ssseg_seg_metrics)."""
+    whole validation set (lovasz.iou, lovasz.py:54-73) from the same device pass (ssseg_seg_metrics; a mask with other
+    than 2 channels takes ssseg_seg_metrics_mc with num_classes from the mask, and logs the per-class IoUs too)."""
     model.eval()
     avg_loss, avg_metric = utils.AverageMeter(), utils.AverageMeter()
     rank = torch.distributed.get_rank() if torch.distributed.is_initialized() else 0
@@ -492,10 +515,12 @@ def validate(model, dataloader, epoch, initial_step, summary_writer, config, dev
     seg = None
     with torch.no_grad():
         for sample in dataloader:
-            if seg is None:
-                seg = ops.SegMetrics(device)
             image = sample['image'].to(device)
             mask = sample['semantic_mask'].to(device)
+            if seg is None:
+                # two-channel masks: the reference's binary metric; any other class count: the C-class kernel, with
+                # the class count taken from the mask
+                seg = ops.SegMetrics(device) if mask.shape[1] == 2 else ops.SegMetricsMC(device, mask.shape[1])
             features, pred_maps = model(image)
             loss = config['train']['loss'](pred_maps, mask)
             # argmax -> one-hot -> nearest resize -> dice (train.py:178-186) + lovasz.iou counts: one kernel
@@ -503,20 +528,32 @@ def validate(model, dataloader, epoch, initial_step, summary_writer, config, dev
             metric = res[0:1].clone()[0]
             avg_loss.update(utils.reduce_tensor(loss.clone()) / world)
             avg_metric.update(utils.reduce_tensor(metric) / world)
-    miou = None
+    miou = class_ious = None
     if seg is not None:
         total = seg.total.clone()
         if world > 1:
             torch.distributed.all_reduce(total)
         t = total.double()
-        ious = [float(t[3] / t[4]) if t[4] else 1., float(t[5] / t[6]) if t[6] else 1.]
-        miou = 100. * sum(ious) / 2
+        if isinstance(seg, ops.SegMetricsMC):
+            # lovasz.iou (lovasz.py:54-73) from the running confusion matrix (rows label, columns prediction)
+            inter = t.diagonal()
+            union = t.sum(0) + t.sum(1) - inter
+            class_ious = [100. * float(i / u) if u else 100. for i, u in zip(inter, union)]
+            miou = sum(class_ious) / len(class_ious)
+        else:
+            ious = [float(t[3] / t[4]) if t[4] else 1., float(t[5] / t[6]) if t[6] else 1.]
+            miou = 100. * sum(ious) / 2
+    _VALIDATE['miou'], _VALIDATE['class_ious'] = miou, class_ious
     if rank == 0:
         print(f'Eval: Epoch: {epoch} Val loss: {avg_loss.average()} Val metric: {avg_metric.average()} mIoU: {miou}')
+        if class_ious is not None:
+            print('Eval: IoU per class: ' + ' '.join(f'{v:.2f}' for v in class_ious))
         if summary_writer is not None:
             summary_writer.add_scalar('val_loss_avg', avg_loss.average(), initial_step)
             summary_writer.add_scalar('val_dice', avg_metric.average(), initial_step)
             if miou is not None:
                 summary_writer.add_scalar('val_miou', miou, initial_step)
+            for c, v in enumerate(class_ious or ()):
+                summary_writer.add_scalar(f'val_iou_class_{c}', v, initial_step)
     model.train()
     return avg_loss.average(), avg_metric.average()

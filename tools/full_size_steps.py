@@ -29,10 +29,12 @@ import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
 # semi-supervised step GFLOP per labelled image (3F sup fwd+bwd + 2F teacher + 3F consistency fwd+bwd)
-STEP_GFLOP_PER_IMAGE = {'c2': 765.1, 'c2geo': 765.1, 'c3': 3855.8, 'c4': 3904.2, 'c5': 85.2}   # (c2geo: the same convs)
+# (c2geo: the same convs; c6: C2's convs with a 19-class head, +0.1 %)
+STEP_GFLOP_PER_IMAGE = {'c2': 765.1, 'c2geo': 765.1, 'c3': 3855.8, 'c4': 3904.2, 'c5': 85.2, 'c6': 765.1}
 PEAK = {'bfloat16': 2.5e15, 'float16': 2.5e15, 'float32': 0.16e15}   # dense MFMA (MI355X_MICROARCH.md)
 CFGS = {'c2': 'configs/c2_unet_r50.py', 'c2geo': 'configs/c2_unet_r50_geo.py', 'c3': 'configs/c3_deeplabv3_r101.py',
-        'c4': 'configs/c4_msa_hrnet.py', 'c5': 'configs/c5_hardnet_disc.py'}
+        'c4': 'configs/c4_msa_hrnet.py', 'c5': 'configs/c5_hardnet_disc.py',
+        'c6': 'configs/c6_unet_r50_multiclass.py'}
 
 
 def train_loop(name, path, dev, threshold, calibrate, n_warm=4, n_timed=10):
@@ -108,7 +110,7 @@ def build(name, path, dev, threshold=0.5, calibrate=True):
                                                                              torch.bfloat16))
     model = DistributedDataParallel(cfg['model']['model_fn']().to(dev))
     if calibrate:
-        rescale_heads(model.module)
+        rescale_heads(model.module, int(cfg['common'].get('num_classes', 2)))
     ema = cfg['model']['model_fn']().to(dev)
     # the teacher starts from the student's weights: the stand-in for the pretrained checkpoint both models load in
     # the reference (distributed_trainer.py:56-61); two independent random inits give a teacher whose eval logits do
@@ -131,8 +133,13 @@ def build(name, path, dev, threshold=0.5, calibrate=True):
     b, s = tc['batch_size_per_worker'], cfg['common']['image_size']
     g = torch.Generator().manual_seed(5)
     img = torch.rand(b, 3, s, s, generator=g).to(dev)
-    fg = (torch.rand(b, 1, s, s, generator=g) > 0.5).float().to(dev)
-    mask = torch.cat([1 - fg, fg], 1).contiguous()
+    ncls = int(cfg['common'].get('num_classes', 2))
+    if ncls == 2:
+        fg = (torch.rand(b, 1, s, s, generator=g) > 0.5).float().to(dev)
+        mask = torch.cat([1 - fg, fg], 1).contiguous()
+    else:   # one-hot of uniform labels
+        label = torch.randint(0, ncls, (b, s, s), generator=g)
+        mask = torch.nn.functional.one_hot(label, ncls).permute(0, 3, 1, 2).float().contiguous().to(dev)
     ua = torch.rand(b, 3, s, s, generator=g).to(dev)
     ub = torch.rand(b, 3, s, s, generator=g).to(dev)
     if calibrate:
