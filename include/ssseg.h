@@ -246,6 +246,14 @@ int ssseg_lovasz_bwd_from_fwd(const float* logits, const float* target, int64_t 
                               const float* gout, float* grad_out, const void* ws, size_t ws_bytes,
                               ssseg_stream_t stream);
 
+/* The segmented sort of the Lovász losses on its own (the same kernel launches in the same order): S segments of equal
+ * length L, keys_in / vals_in [S][L] u32 -> keys_out / vals_out [S][L], each segment ascending by key and stable
+ * (equal keys keep their input order).  The inputs are not modified; keys_out / vals_out may be keys_in / vals_in.
+ * Bounds: 1 <= S <= 65535, 1 <= L <= 2^24, else SSSEG_EINVAL (workspace_bytes returns 0). */
+size_t ssseg_lovasz_sort_workspace_bytes(int64_t S, int64_t L);
+int ssseg_lovasz_sort(const unsigned* keys_in, const unsigned* vals_in, unsigned* keys_out, unsigned* vals_out,
+                      int64_t S, int64_t L, void* ws, size_t ws_bytes, ssseg_stream_t stream);
+
 /* General Lovász losses (lovasz.py:79-127, 155-220) on the device, no host synchronisation.
  * x [B,C,HW] f32: class probabilities (SSSEG_LOVASZ_PROBAS; C == 1 is the reference's sigmoid case, channel 0 is the
  * prediction of the one selected class), logits with the softmax over C fused (SSSEG_LOVASZ_SOFTMAX, C >= 2), or

@@ -322,6 +322,27 @@ struct Ws {
 
 int64_t tiles_of(int64_t HW) { return (HW + TILE - 1) / TILE; }
 
+// The segmented sort: S segments of equal length L, ascending by key and stable, four passes of 8-bit digits.
+// Pass 0 reads (kin, vin) and writes (ktmp, vtmp); the passes then alternate (kout, vout) and (ktmp, vtmp), so the
+// sorted data ends in (kout, vout).  (kout, vout) may be (kin, vin): pass 0 has read them before pass 1 writes.
+// hist: 256*S*T words, dtot: 4*256*S words (zeroed here).  1 <= S <= 65535 (gridDim.y), 1 <= L <= 2^24.
+void seg_sort(const unsigned* kin, const unsigned* vin, unsigned* ktmp, unsigned* vtmp, unsigned* kout, unsigned* vout,
+              unsigned S, int64_t L, unsigned* hist, unsigned* dtot_all, hipStream_t s) {
+  const int T = (int)tiles_of(L);
+  (void)hipMemsetAsync(dtot_all, 0, sizeof(unsigned) * (size_t)S * 256 * 4, s);   // the four passes' digit totals
+  unsigned *kdst = ktmp, *vdst = vtmp;
+  for (int pass = 0; pass < 4; ++pass) {
+    const int shift = 8 * pass;
+    unsigned* dtot = dtot_all + (size_t)pass * S * 256;
+    hipLaunchKernelGGL(radix_hist_kernel, dim3(T, S), dim3(LT), 0, s, kin, L, T, shift, hist, dtot);
+    hipLaunchKernelGGL(seg_rowscan_kernel, dim3(64, S), dim3(256), 0, s, hist, dtot, T);
+    hipLaunchKernelGGL(radix_scatter_kernel, dim3(T, S), dim3(LT), 0, s, kin, vin, kdst, vdst, L, T, shift, hist);
+    kin = kdst; vin = vdst;
+    kdst = kdst == ktmp ? kout : ktmp;
+    vdst = vdst == vtmp ? vout : vtmp;
+  }
+}
+
 size_t ws_layout(int64_t B, int64_t HW, char* p, Ws* w) {
   const int64_t n = B * HW, T = tiles_of(HW);
   size_t off = 0;
@@ -355,19 +376,7 @@ int lovasz_core(const float* logits, const float* target, int64_t B, int64_t C, 
   const int T = (int)tiles_of(HW);
   hipLaunchKernelGGL(lovasz_prep_kernel, dim3(ssseg_grid(n, 256)), dim3(256), 0, s, logits, target, B, (int)C, HW,
                      w.ka, w.va);
-  unsigned *kin = w.ka, *vin = w.va, *kout = w.kb, *vout = w.vb;
-  (void)hipMemsetAsync(w.dtot, 0, sizeof(unsigned) * (size_t)B * 256 * 4, s);   // the four passes' digit totals
-  for (int pass = 0; pass < 4; ++pass) {
-    const int shift = 8 * pass;
-    unsigned* dtot = w.dtot + (size_t)pass * B * 256;
-    hipLaunchKernelGGL(radix_hist_kernel, dim3(T, (unsigned)B), dim3(LT), 0, s, kin, HW, T, shift, w.hist, dtot);
-    hipLaunchKernelGGL(seg_rowscan_kernel, dim3(64, (unsigned)B), dim3(256), 0, s, w.hist, dtot, T);
-    hipLaunchKernelGGL(radix_scatter_kernel, dim3(T, (unsigned)B), dim3(LT), 0, s, kin, vin, kout, vout, HW, T, shift,
-                       w.hist);
-    unsigned* tk = kin; kin = kout; kout = tk;
-    unsigned* tv = vin; vin = vout; vout = tv;
-  }
-  // 4 passes: sorted data is back in (ka, va)
+  seg_sort(w.ka, w.va, w.kb, w.vb, w.ka, w.va, (unsigned)B, HW, w.hist, w.dtot, s);   // sorted data back in (ka, va)
   hipLaunchKernelGGL(fg_count_kernel, dim3(T, (unsigned)B), dim3(LT), 0, s, w.va, HW, T, w.tile_fg);
   hipLaunchKernelGGL(fg_scan_kernel, dim3((unsigned)B), dim3(64), 0, s, w.tile_fg, T);
   hipLaunchKernelGGL(lovasz_grad_kernel, dim3(T, (unsigned)B), dim3(LT), 0, s, w.ka, w.va, HW, T, w.tile_fg, w.gpix,
@@ -419,6 +428,47 @@ extern "C" int ssseg_lovasz_bwd_from_fwd(const float* logits, const float* targe
   ws_layout(B, HW, (char*)ws, &w);
   hipLaunchKernelGGL(lovasz_bwd_kernel, dim3(ssseg_grid(B * HW, 256)), dim3(256), 0, (hipStream_t)stream, logits,
                      target, B, (int)C, HW, w.gpix, w.wscale, gout, grad_out);
+  SSSEG_LAUNCH_CHECK();
+  return 0;
+}
+
+// The losses' segmented sort on its own (seg_sort above, the same launches): workspace = one more pair of key / value
+// buffers, the digit tables and the digit totals.
+namespace {
+size_t sort_ws_layout(int64_t S, int64_t L, char* p, unsigned** ktmp, unsigned** vtmp, unsigned** hist,
+                      unsigned** dtot) {
+  const int64_t T = tiles_of(L);
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    char* q = p ? p + off : nullptr;
+    off += (bytes + 255) / 256 * 256;
+    return (unsigned*)q;
+  };
+  unsigned* k = take(4 * (size_t)S * L);
+  unsigned* v = take(4 * (size_t)S * L);
+  unsigned* h = take(4 * (size_t)S * 256 * T);
+  unsigned* d = take(4 * (size_t)S * 256 * 4);
+  if (p) {
+    *ktmp = k; *vtmp = v; *hist = h; *dtot = d;
+  }
+  return off;
+}
+}  // namespace
+
+extern "C" size_t ssseg_lovasz_sort_workspace_bytes(int64_t S, int64_t L) {
+  if (S < 1 || S > 65535 || L < 1 || L > ((int64_t)1 << 24)) return 0;
+  return sort_ws_layout(S, L, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int ssseg_lovasz_sort(const unsigned* keys_in, const unsigned* vals_in, unsigned* keys_out,
+                                 unsigned* vals_out, int64_t S, int64_t L, void* ws, size_t ws_bytes,
+                                 ssseg_stream_t stream) {
+  if (!keys_in || !vals_in || !keys_out || !vals_out || S < 1 || S > 65535 || L < 1 || L > ((int64_t)1 << 24))
+    return SSSEG_EINVAL;
+  if (!ws || ws_bytes < ssseg_lovasz_sort_workspace_bytes(S, L)) return SSSEG_EWORKSPACE;
+  unsigned *ktmp, *vtmp, *hist, *dtot;
+  sort_ws_layout(S, L, (char*)ws, &ktmp, &vtmp, &hist, &dtot);
+  seg_sort(keys_in, vals_in, ktmp, vtmp, keys_out, vals_out, (unsigned)S, L, hist, dtot, (hipStream_t)stream);
   SSSEG_LAUNCH_CHECK();
   return 0;
 }
@@ -824,17 +874,7 @@ void gen_core(const GenArgs& a, const GenSel& sel, float* loss_out, GenWs& w, hi
     const int kn = K - k0 < Kc ? K - k0 : Kc;
     const unsigned S = (unsigned)(G * kn);
     hipLaunchKernelGGL(lovasz_gen_prep_kernel, dim3(ssseg_grid(N, 256)), dim3(256), 0, s, a, sel, k0, kn, w.ka, w.va);
-    unsigned *kin = w.ka, *vin = w.va, *kout = w.kb, *vout = w.vb;
-    (void)hipMemsetAsync(w.dtot, 0, sizeof(unsigned) * (size_t)S * 256 * 4, s);
-    for (int pass = 0; pass < 4; ++pass) {
-      const int shift = 8 * pass;
-      unsigned* dtot = w.dtot + (size_t)pass * S * 256;
-      hipLaunchKernelGGL(radix_hist_kernel, dim3(T, S), dim3(LT), 0, s, kin, L, T, shift, w.hist, dtot);
-      hipLaunchKernelGGL(seg_rowscan_kernel, dim3(64, S), dim3(256), 0, s, w.hist, dtot, T);
-      hipLaunchKernelGGL(radix_scatter_kernel, dim3(T, S), dim3(LT), 0, s, kin, vin, kout, vout, L, T, shift, w.hist);
-      unsigned* tk = kin; kin = kout; kout = tk;
-      unsigned* tv = vin; vin = vout; vout = tv;
-    }
+    seg_sort(w.ka, w.va, w.kb, w.vb, w.ka, w.va, S, L, w.hist, w.dtot, s);
     hipLaunchKernelGGL(fg_count_kernel, dim3(T, S), dim3(LT), 0, s, w.va, L, T, w.tile_fg);
     hipLaunchKernelGGL(fg_scan_kernel, dim3(S), dim3(64), 0, s, w.tile_fg, T);
     hipLaunchKernelGGL(lovasz_gen_grad_kernel, dim3(T, S), dim3(LT), 0, s, w.ka, w.va, L, T, G, a.C,

@@ -71,6 +71,8 @@ SIGS = {
     'ssseg_lovasz_fwd': (i32, [vp, vp, i64, i64, i64, vp, vp, sz, vp]),
     'ssseg_lovasz_bwd': (i32, [vp, vp, i64, i64, i64, vp, vp, vp, sz, vp]),
     'ssseg_lovasz_bwd_from_fwd': (i32, [vp, vp, i64, i64, i64, vp, vp, vp, sz, vp]),
+    'ssseg_lovasz_sort_workspace_bytes': (sz, [i64, i64]),
+    'ssseg_lovasz_sort': (i32, [vp, vp, vp, vp, i64, i64, vp, sz, vp]),
     'ssseg_lovasz_gen_workspace_bytes': (sz, [i64, i64, i64, i32, i64]),
     'ssseg_lovasz_gen_fwd': (i32, [vp, vp, i32, i64, i64, i64, i32, i32, i32, I64P, i64, i32, i64, vp, vp, sz, vp]),
     'ssseg_lovasz_gen_bwd': (i32, [vp, vp, i32, i64, i64, i64, i32, i32, i32, I64P, i64, i32, i64, vp, vp, vp, sz,
