@@ -75,6 +75,40 @@ int ssseg_mix(const void* a, const void* b, const float* mask, void* out, int64_
               int64_t HW, int dt, ssseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * ClassMix and CutMix masks for the consistency branch (build-defined: the reference has CowMix only;
+ * Olsson et al. 2021, French et al. 2020).  Both write a float mask [B,1,H,W] in {0,1} for ssseg_mix.
+ * ------------------------------------------------------------------------------------------- */
+
+/* Workspace bytes for ssseg_classmix_mask(B, H, W): one label byte per pixel plus the per-image state
+ * (0 for a non-positive size). */
+size_t ssseg_classmix_workspace_bytes(int64_t B, int64_t H, int64_t W);
+
+/* ClassMix: label = argmax_c logits (first maximum wins, NaN counts as the maximum); per image the set of
+ * present labels (n of them); chosen = the k = ceil(n/2) present classes with the smallest (keys[b,c], c),
+ * keys compared as signed int32; mask = 1 where the pixel's label is chosen.
+ * logits [B,C,H,W] of dtype `dt` at element strides strides4 (batch, channel, row, column) whose pixels lie at
+ * one stride (row stride == W * column stride: NCHW-contiguous and channels-last; else SSSEG_EUNSUPPORTED),
+ * 1 <= C <= 64, B <= 65535; keys [B,C] int32 in [0, 2^31); mask_out [B,H,W] f32; present_out, chosen_out (nullable) [B]
+ * 64-bit words, bit c = class c. */
+int ssseg_classmix_mask(const void* logits, const int64_t* strides4, int dt, const int* keys, int64_t B, int64_t C,
+                        int64_t H, int64_t W, float* mask_out, unsigned long long* present_out,
+                        unsigned long long* chosen_out, void* workspace, size_t workspace_bytes,
+                        ssseg_stream_t stream);
+
+/* CutMix: per image the uniforms params[b] = (p', u, v1, v2) in [0,1) give, in fp64 with rint (half to even),
+ *   p = lo + (hi-lo) p',  h = rint(H p^u),  w = rint(W p^(1-u)),  top = rint((H-h) v1),  left = rint((W-w) v2);
+ * mask_out [B,H,W] f32 is 1 inside the box; boxes_out (nullable) [B,4] int32 = top, left, h, w.
+ * 0 <= lo <= hi <= 1, H*W < 2^31. */
+int ssseg_cutmix_mask(const float* params, int64_t B, int64_t H, int64_t W, double lo, double hi, float* mask_out,
+                      int* boxes_out, ssseg_stream_t stream);
+
+/* The random inputs of both masks from Philox on CowMix's seed and device counter (streams 3 and 4 of the key):
+ * keys (nullable) [B,C] int32 in [0, 2^31), params (nullable) [B,4] f32 in [0,1); at least one is given.  The
+ * counter is advanced on the device by B * (ceil(C/4) + 1) whichever outputs are asked for. */
+int ssseg_mixmask_draw_dev(int* keys, float* params, int64_t B, int64_t C, uint64_t seed,
+                           unsigned long long* offset_dev, ssseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Layout / dtype conversion (model input/output boundary; the reference feeds NCHW fp32)
  * ------------------------------------------------------------------------------------------- */
 

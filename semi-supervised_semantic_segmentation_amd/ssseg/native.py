@@ -41,6 +41,10 @@ SIGS = {
     'ssseg_mix': (i32, [vp, vp, vp, vp, i64, i64, i64, i32, vp]),
     'ssseg_cowmix_draw': (i32, [vp, vp, vp, i64, i64, f64, f64, f64, f64, u64, u64, vp]),
     'ssseg_cowmix_draw_dev': (i32, [vp, vp, vp, i64, i64, f64, f64, f64, f64, u64, vp, vp]),
+    'ssseg_classmix_workspace_bytes': (sz, [i64, i64, i64]),
+    'ssseg_classmix_mask': (i32, [vp, I64P, i32, vp, i64, i64, i64, i64, vp, vp, vp, vp, sz, vp]),
+    'ssseg_cutmix_mask': (i32, [vp, i64, i64, i64, f64, f64, vp, vp, vp]),
+    'ssseg_mixmask_draw_dev': (i32, [vp, vp, i64, i64, u64, vp, vp]),
     'ssseg_nchw_to_nhwc': (i32, [vp, vp, i64, i64, i64, i64, i64, i32, i32, vp]),
     'ssseg_nhwc_to_nchw': (i32, [vp, vp, i64, i64, i64, i64, i64, i32, i32, vp]),
     'ssseg_cast': (i32, [vp, vp, i64, i32, i32, vp]),

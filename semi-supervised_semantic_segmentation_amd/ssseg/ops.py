@@ -58,6 +58,53 @@ def mix(a, b, mask):
     return out
 
 
+def classmix_mask(teacher_logits, keys, return_state=False):
+    """ClassMix mask (Olsson et al. 2021) of the teacher's logits [B,C,H,W] (fp32, bf16 or fp16; 1 <= C <= 64): the
+    label of a pixel is its argmax (first maximum wins, NaN counts as the maximum); per image, of the n classes
+    present, the ceil(n/2) with the smallest (keys[b,c], c) are chosen; mask [B,1,H,W] f32 is 1 on their pixels.
+    keys [B,C] integers in [0, 2^31).  return_state: also (present, chosen) [B] int64, bit c = class c."""
+    x = teacher_logits
+    if x.dim() != 4:
+        raise ValueError(f'classmix_mask: logits must be [B,C,H,W], got {tuple(x.shape)}')
+    B, C, H, W = x.shape
+    if not 1 <= C <= 64:
+        raise ValueError(f'classmix_mask: {C} channels (1 to 64 are supported)')
+    if tuple(keys.shape) != (B, C):
+        raise ValueError(f'classmix_mask: keys must be [B,C] = {(B, C)}, got {tuple(keys.shape)}')
+    with torch.no_grad():
+        x = x.detach()
+        if x.stride(2) != W * x.stride(3) and H != 1:
+            x = x.contiguous()   # the kernel walks the pixels of an image at one stride (NCHW and channels-last do)
+        keys = _c(keys.to(torch.int32))
+        mask = torch.empty(B, 1, H, W, device=x.device, dtype=torch.float32)
+        present = torch.empty(B, device=x.device, dtype=torch.int64) if return_state else None
+        chosen = torch.empty(B, device=x.device, dtype=torch.int64) if return_state else None
+        nb = N.lib().ssseg_classmix_workspace_bytes(B, H, W)
+        ws = N.workspace(nb, x.device)
+        N.call('ssseg_classmix_mask', N.dev_ptr(x, 'logits'), N.strides4(x), N.dt_code(x), N.dev_ptr(keys, 'keys'), B,
+               C, H, W, N.dev_ptr(mask), N.dev_ptr(present), N.dev_ptr(chosen), N.dev_ptr(ws), nb, N.stream())
+    return (mask, present, chosen) if return_state else mask
+
+
+def cutmix_mask(params, H, W, mask_proportion_range, return_boxes=False):
+    """CutMix mask (French et al. 2020): params [B,4] uniforms (p', u, v1, v2) in [0,1) -> mask [B,1,H,W] f32, 1 inside
+    the box  p = lo + (hi-lo) p', h = rint(H p^u), w = rint(W p^(1-u)), top = rint((H-h) v1), left = rint((W-w) v2)
+    (fp64, half to even).  return_boxes: also [B,4] int32 (top, left, h, w)."""
+    if params.dim() != 2 or params.shape[1] != 4:
+        raise ValueError(f'cutmix_mask: params must be [B,4], got {tuple(params.shape)}')
+    lo, hi = float(mask_proportion_range[0]), float(mask_proportion_range[1])
+    if not 0.0 <= lo <= hi <= 1.0:
+        raise ValueError(f'cutmix_mask: mask_proportion_range {mask_proportion_range!r} is not 0 <= lo <= hi <= 1')
+    with torch.no_grad():
+        params = _c(params.detach().float())
+        B = params.shape[0]
+        mask = torch.empty(B, 1, H, W, device=params.device, dtype=torch.float32)
+        boxes = torch.empty(B, 4, device=params.device, dtype=torch.int32) if return_boxes else None
+        N.call('ssseg_cutmix_mask', N.dev_ptr(params, 'params'), B, H, W, lo, hi, N.dev_ptr(mask), N.dev_ptr(boxes),
+               N.stream())
+    return (mask, boxes) if return_boxes else mask
+
+
 # ------------------------------------------------------------------------------------------------
 # Bilinear interpolation (F.interpolate mode='bilinear')
 # ------------------------------------------------------------------------------------------------

@@ -19,6 +19,7 @@ import torch
 import cowmix
 import mean_teacher
 import metrics
+import mixmasks
 import utils.utils as utils
 from ssseg import nn as snn
 from ssseg import ops
@@ -128,7 +129,9 @@ def _step_key(model, ema_model, image, unsup_a):
 
 def _teacher_targets(ema_model, unsup_a, unsup_b, tc):
     """train.py:66-85: the teacher's predictions on both unlabelled batches (no grad, eval), resized to the image size,
-    the CowMix mask and the two mixes.  Returns (mixed teacher logits, mixed images)."""
+    the mixing mask (config['train']['mix_mask']: CowMix, the reference's and the default; CutMix; or ClassMix, cut
+    from the teacher's own prediction on batch A) and the two mixes.  Returns (mixed teacher logits, mixed images)."""
+    kind = mixmasks.mix_mask_kind(tc)
     size = unsup_a.shape[2:4]
     with torch.no_grad(), snn.folded(_inner(ema_model)):   # one batched BN fold for both teacher passes
         if _batched_eval_ok(ema_model, unsup_a, unsup_b):
@@ -144,8 +147,13 @@ def _teacher_targets(ema_model, unsup_a, unsup_b, tc):
         else:
             ema_pred_a = ops.interpolate_bilinear(ema_model(unsup_a)[-1][-1], size, align_corners=False)
             ema_pred_b = ops.interpolate_bilinear(ema_model(unsup_b)[-1][-1], size, align_corners=False)
-        cmask = cowmix.generate_cowmix_masks_like(unsup_a, mask_proportion_range=tc['mask_proportion_range'],
-                                                  sigma_range=tc['sigma_range'])
+        if kind == 'classmix':
+            cmask = mixmasks.generate_classmix_masks_like(ema_pred_a)
+        elif kind == 'cutmix':
+            cmask = mixmasks.generate_cutmix_masks_like(unsup_a, tc['mask_proportion_range'])
+        else:
+            cmask = cowmix.generate_cowmix_masks_like(unsup_a, mask_proportion_range=tc['mask_proportion_range'],
+                                                      sigma_range=tc['sigma_range'])
         mixed_ema_pred = cowmix.mix_with_mask(ema_pred_a, ema_pred_b, cmask)
         mixed_images = cowmix.mix_with_mask(unsup_a, unsup_b, cmask)
     return mixed_ema_pred, mixed_images
@@ -224,6 +232,8 @@ def train_step(model, ema_model, optimizer, image, mask, unsup_a, unsup_b, epoch
     ddp = model if isinstance(model, _DDP) else None
     semi = tc['use_semi_supervised']
     adv = tc.get('adversarial')
+    if semi:
+        mixmasks.mix_mask_kind(tc)   # an unknown mask is refused before anything is launched
     features, pred_maps = model(image)
     classification_loss = tc['loss'](pred_maps, mask)
     sup_loss = classification_loss
@@ -333,9 +343,10 @@ def train_step(model, ema_model, optimizer, image, mask, unsup_a, unsup_b, epoch
 # the benchmark: C5 (HarDNet + discriminator, ~660 small launches) 63.6 -> 33.5 ms/step, C4 213 -> 195 ms.  A replay
 # repeats the Python decisions of its capture, so the graph is keyed on every one of them: the optimizer step taken
 # or skipped (train.py:121, step % virtual_batch_size_multiplier), the epoch gate of the consistency weight
-# (train.py:112), the consistency activation, every learning rate, the input geometry and compute dtype -- a new key
+# (train.py:112), the consistency activation, the mixing mask, every learning rate, the input geometry and compute dtype -- a new key
 # captures a new graph (the two
-# most recent are kept).  Not captured (eager steps instead): CowMix drawn from the CPU generator (parity mode), a
+# most recent are kept).  Not captured (eager steps instead): CowMix drawn from the CPU generator (parity mode),
+# ClassMix / CutMix draws from the host generator or fixed (mixmasks.DRAW_SOURCE, set_draws), a
 # consistency augmentation whose parameters come from the host (source='cpu' or set_params), steps
 # with collectives on torch.distributed (gloo, or SSSEG_COMM=c10d: the native RCCL communicator's steps ARE captured),
 # the first optimizer step (SGD's momentum buffer starts from it),
@@ -359,6 +370,9 @@ def _graph_key(model, ema_model, optimizer, image, mask, unsup_a, unsup_b, epoch
         return None
     if tc['use_semi_supervised'] and cowmix.NOISE_SOURCE != 'device':
         return None
+    kind = mixmasks.mix_mask_kind(tc) if tc['use_semi_supervised'] else 'cowmix'
+    if not mixmasks.capturable(kind):
+        return None   # ClassMix / CutMix draws from the host generator, or fixed: a replay would repeat them
     aug = _consistency_augmentation(tc) if tc['use_semi_supervised'] else None
     if aug is not None and (aug.source != 'device' or aug.fixed is not None):
         return None   # parameters drawn or uploaded on the host: a replay would repeat them
@@ -380,7 +394,7 @@ def _graph_key(model, ema_model, optimizer, image, mask, unsup_a, unsup_b, epoch
     lrs = tuple(float(g['lr']) for o in opts for g in o.param_groups)
     shapes = tuple((tuple(t.shape), t.dtype) if t is not None else None for t in (image, mask, unsup_a, unsup_b))
     return step_key + (id(optimizer), opt_step, float(epoch > 25), lrs, shapes, id(config),
-                       _consistency_activation(tc))
+                       _consistency_activation(tc), kind)
 
 
 def _graph_step(key, model, ema_model, optimizer, image, mask, unsup_a, unsup_b, epoch, step, config):

@@ -30,11 +30,14 @@ import torch.distributed as dist  # noqa: E402
 
 # semi-supervised step GFLOP per labelled image (3F sup fwd+bwd + 2F teacher + 3F consistency fwd+bwd)
 # (c2geo: the same convs; c6: C2's convs with a 19-class head, +0.1 %)
-STEP_GFLOP_PER_IMAGE = {'c2': 765.1, 'c2geo': 765.1, 'c3': 3855.8, 'c4': 3904.2, 'c5': 85.2, 'c6': 765.1}
+STEP_GFLOP_PER_IMAGE = {'c2': 765.1, 'c2geo': 765.1, 'c2cutmix': 765.1, 'c3': 3855.8, 'c4': 3904.2, 'c5': 85.2, 'c6': 765.1,
+                        'c6classmix': 765.1}
 PEAK = {'bfloat16': 2.5e15, 'float16': 2.5e15, 'float32': 0.16e15}   # dense MFMA (MI355X_MICROARCH.md)
 CFGS = {'c2': 'configs/c2_unet_r50.py', 'c2geo': 'configs/c2_unet_r50_geo.py', 'c3': 'configs/c3_deeplabv3_r101.py',
         'c4': 'configs/c4_msa_hrnet.py', 'c5': 'configs/c5_hardnet_disc.py',
-        'c6': 'configs/c6_unet_r50_multiclass.py'}
+        'c6': 'configs/c6_unet_r50_multiclass.py', 'c6classmix': 'configs/c6_unet_r50_classmix.py',
+        'c2cutmix': 'configs/c2_unet_r50_cutmix.py'}
+MIX_MASK = {'kind': None}   # --mix-mask: the mixing mask of every config of the run (train['mix_mask'])
 
 
 def train_loop(name, path, dev, threshold, calibrate, n_warm=4, n_timed=10):
@@ -124,6 +127,8 @@ def build(name, path, dev, threshold=0.5, calibrate=True):
     tc = cfg['train']
     tc['confidence_threshold'] = threshold
     tc['print_freq'] = 10 ** 9
+    if MIX_MASK['kind'] is not None:
+        tc['mix_mask'] = MIX_MASK['kind']
     if cfg['model'].get('discriminator') is not None and tc.get('adversarial_loss_weight'):
         disc = DistributedDataParallel(cfg['model']['discriminator']().to(dev))
         dopt = soptim.from_config(tc['discriminator_optimizer'], disc.parameters())
@@ -208,7 +213,7 @@ def run(name, path, dev, threshold=0.5, calibrate=True, layers=False, graph=Fals
     params_finite = all(bool(torch.isfinite(p).all()) for p in model.parameters())
     losses_finite = all(v is None or v == v and abs(v) != float('inf') for row in out for v in row)
     rec = {'config': name, 'image_size': s, 'batch': b, 'dtype': str(snn.compute_dtype()).replace('torch.', ''),
-           'confidence_threshold': threshold, 'bn_calibrated': calibrate,
+           'confidence_threshold': threshold, 'bn_calibrated': calibrate, 'mix_mask': tc.get('mix_mask', 'cowmix'),
            'cm_mean': [row[2] for row in out], 'losses': out, 'losses_finite': losses_finite, 'params_finite': params_finite,
            'ms_per_step_last2': round(1e3 * sum(times[-2:]) / 2, 1), 'first_step_s': round(times[0], 1),
            'peak_mem_GB': round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 1),
@@ -251,7 +256,9 @@ def main():
     ap.add_argument('--collectives', action='store_true', help='world 1 with the DDP bucket all-reduces and SyncBN sums '
                     'forced on (ssseg.ddp.force_collectives): the multi-GPU step\'s collectives on the native RCCL '
                     'communicator, eager and captured')
+    ap.add_argument('--mix-mask', choices=('cowmix', 'cutmix', 'classmix'), help="train['mix_mask'] of every config")
     a = ap.parse_args()
+    MIX_MASK['kind'] = a.mix_mask
     dev = torch.device('cuda', 0)
     torch.cuda.set_device(dev)
     dist.init_process_group('nccl', init_method='tcp://127.0.0.1:29533', rank=0, world_size=1)
