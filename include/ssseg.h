@@ -260,6 +260,27 @@ int ssseg_consistency_sm_fwd(const float* s, const float* t, const float* w, int
                              float thr, float* out3, void* ws, size_t ws_bytes, ssseg_stream_t stream);
 int ssseg_consistency_sm_bwd(const float* s, const float* t, const float* w, int64_t B, int64_t C, int64_t HW,
                              float thr, const float* out3, const float* gout, float* gs, ssseg_stream_t stream);
+/* Pseudo-label consistency (csrc/multiclass.hip): cross-entropy of the student against the teacher's hard label,
+ * weighted by the teacher's confidence (FixMatch, ClassMix, CutMix-Seg).  The operand contract of
+ * ssseg_consistency_sm_*: s, t [B,C,HW] f32 contiguous, 1 <= C <= 64 (SSSEG_EINVAL otherwise); w [B,HW] f32 or NULL
+ * (NULL gives the bits of w == 1); weighting 0 = 'pixel', 1 = 'batch' (SSSEG_EINVAL otherwise).  Per pixel i:
+ *   y = argmax_c t_c (the first maximum wins, NaN counts as the maximum, the first NaN wins),
+ *   conf = 1 / sum_c exp(t_c - max t) (= max_c softmax(t)),  cm = [conf > thr] in fp32,
+ *   ce = log sum_c exp(s_c - max s) + max s - s_y;
+ * over the batch N_w = sum w, S_cm = sum w cm, S_conf = sum w cm ce, S_all = sum w ce (fp64 partials, two stages).
+ *   'pixel': out4[0] = S_conf / N_w, a pixel with cm == 0 selected out (it adds exactly 0 whatever its ce: the loss is
+ *            0.0, not NaN, when no pixel is confident);   'batch': out4[0] = (S_cm / N_w) (S_all / N_w);
+ *   out4[1] = S_cm / (B HW);  out4[2] = S_cm;  out4[3] = N_w (N_w == 0 gives NaN).
+ * gs_c = gout[0] k (softmax(s)_c - [c == y]) with k = w cm / out4[3] ('pixel': exact zeros where cm == 0) or
+ * k = (out4[2] / out4[3]) w / out4[3] ('batch': the confident fraction is a constant of the teacher); gs is
+ * overwritten.  Workspace: ssseg_consistency_ce_workspace_bytes(B*HW) (three partials per workgroup: N_w, S_cm
+ * and the one of S_conf / S_all that the weighting reads). */
+size_t ssseg_consistency_ce_workspace_bytes(int64_t n);
+int ssseg_consistency_ce_fwd(const float* s, const float* t, const float* w, int64_t B, int64_t C, int64_t HW,
+                             float thr, int weighting, float* out4, void* ws, size_t ws_bytes, ssseg_stream_t stream);
+int ssseg_consistency_ce_bwd(const float* s, const float* t, const float* w, int64_t B, int64_t C, int64_t HW,
+                             float thr, int weighting, const float* out4, const float* gout, float* gs,
+                             ssseg_stream_t stream);
 
 /* Binary Lovász (losses.binary_lovasz_loss_with_logits losses.py:239-250 -> lovasz_softmax
  * lovasz.py:155-201 with classes=[1], per_image=True).  logits, target [B,C,HW] f32, 1 <= B <= 4096.

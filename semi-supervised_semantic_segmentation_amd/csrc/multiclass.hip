@@ -1,5 +1,6 @@
 // The multi-class (2 <= C <= 64 mutually exclusive classes) forms of the semi-supervised step's two-class kernels:
 //   softmax consistency loss  (train.py:97-108 with the softmax lines :97,:99 in place of the sigmoid ones),
+//   pseudo-label consistency  (cross-entropy against the teacher's hard label, weighted by its confidence),
 //   C-class validation metrics (train.py:171-175 with num_classes = C, lovasz.iou lovasz.py:54-73),
 //   C-class inference head     (models/inference_wrapper.py:17-24).
 // Conventions of eltwise.hip / seglosses.hip: contiguous fp32 [B,C,HW], per-block fp64 partials + one final block in
@@ -147,6 +148,203 @@ __global__ void __launch_bounds__(SM_TILE) cons_sm_bwd_kernel(const float* __res
 #pragma unroll
     for (int c = 0; c < CMAX; ++c)
       if (c < C) gp[(int64_t)c * HW] = k * (px.ps[c] * ((px.ps[c] - px.pt[c]) - dot));
+  }
+}
+
+// ---- pseudo-label consistency: confidence-weighted cross-entropy ---------------------------------------------------
+// The student is trained with cross-entropy against the teacher's hard label y = argmax_c t_c, weighted by the
+// teacher's confidence conf = max_c softmax(t) = 1 / sum_c exp(t_c - max t) (FixMatch: per pixel, 'pixel'; ClassMix:
+// the batch's confident fraction, 'batch').  The same tile walk as above.  The forward needs no C-wide row: both
+// operands stream through K-channel chunks (K = 2, 4, 8; 2 * K loads in flight per thread) into a running maximum and a
+// rescaled sum each, and the student logit at the teacher's running argmax is picked on the way.  The backward needs
+// softmax(s) at every channel and keeps the student row in registers (the channel buckets above); its teacher pass is
+// the forward's chunk for chunk, so that both decide conf > thr from the same bits.
+constexpr int CE_SUMS = 3;   // N_w, S_cm and S_conf ('pixel') or S_all ('batch'): partials per workgroup
+
+// running maximum m and sum z = sum_c exp(v_c - m) over the channels seen so far; channels >= C are left out.  FIRST:
+// the chunk at channel 0, which has nothing to rescale.  FAST: the hardware exponential (v_exp_f32 of x log2 e:
+// relative error about 2^-23 (1 + |x|) on these arguments <= 0) -- the teacher's sum feeds one comparison, conf > thr,
+// and nothing else, and its exponentials were a sixth of the backward's time at 19 classes; the student's sums, which
+// feed the loss and the gradient, take expf
+template <bool FAST>
+__device__ __forceinline__ float ce_exp(float x) {
+  return FAST ? __expf(x) : expf(x);
+}
+
+template <int K, bool FIRST, bool FAST>
+__device__ __forceinline__ void ce_absorb(float& m, float& z, const float (&v)[K], int c0, int C) {
+  float mx = FIRST ? v[0] : m;
+#pragma unroll
+  for (int k = FIRST ? 1 : 0; k < K; ++k)
+    if (c0 + k < C) mx = fmaxf(mx, v[k]);
+  float acc = 0.f;
+#pragma unroll
+  for (int k = 0; k < K; ++k) acc += c0 + k < C ? ce_exp<FAST>(v[k] - mx) : 0.f;
+  z = FIRST ? acc : fmaf(z, ce_exp<FAST>(m - mx), acc);
+  m = mx;
+}
+
+// torch.argmax over the channels, chunk after chunk (argmax_c's rule: the first maximum wins, NaN counts as the
+// maximum, the first NaN wins); `pick` follows the winner (the student's logit at that channel)
+template <int K, bool FIRST>
+__device__ __forceinline__ void ce_argmax(float& best, int& arg, float& pick, const float (&tv)[K],
+                                          const float (&sv)[K], int c0, int C) {
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const int c = c0 + k;
+    const float v = tv[k];
+    const bool take = (FIRST && k == 0) || (c < C && (v > best || (v != v && best == best)));
+    best = take ? v : best;
+    arg = take ? c : arg;
+    pick = take ? sv[k] : pick;
+  }
+}
+
+// one pixel's running state of the forward, fed K channels of both operands at a time
+struct CePixel {
+  float mt, zt, ms, zs, best, sy;
+  int arg;
+
+  template <int K, bool FIRST>
+  __device__ __forceinline__ void chunk(const float* __restrict__ sp, const float* __restrict__ tp, int c0, int C,
+                                        int64_t HW) {
+    float sv[K], tv[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      // clamped address instead of a branch around the load: the whole chunk stays in flight together
+      const int64_t o = (int64_t)(c0 + k < C ? c0 + k : c0) * HW;
+      sv[k] = sp[o];
+      tv[k] = tp[o];
+    }
+    ce_argmax<K, FIRST>(best, arg, sy, tv, sv, c0, C);
+    ce_absorb<K, FIRST, true>(mt, zt, tv, c0, C);
+    ce_absorb<K, FIRST, false>(ms, zs, sv, c0, C);
+  }
+};
+
+template <int K>
+__global__ void __launch_bounds__(SM_TILE) cons_ce_partial_kernel(const float* __restrict__ s,
+                                                                  const float* __restrict__ t,
+                                                                  const float* __restrict__ w, int C, int64_t HW,
+                                                                  int64_t tiles_per_sample, int64_t ntiles, float thr,
+                                                                  int weighting, double* __restrict__ part) {
+  __shared__ double red[CE_SUMS][SM_TILE / 64];
+  double nw = 0.0, scm = 0.0, sce = 0.0;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t b = tile / tiles_per_sample;
+    const int64_t pix = (tile - b * tiles_per_sample) * SM_TILE + threadIdx.x;
+    if (pix < HW) {
+      const float* sp = s + b * C * HW + pix;
+      const float* tp = t + b * C * HW + pix;
+      const float wv = w ? w[b * HW + pix] : 1.f;
+      CePixel px;
+      px.chunk<K, true>(sp, tp, 0, C, HW);
+      for (int c0 = K; c0 < C; c0 += K) px.chunk<K, false>(sp, tp, c0, C, HW);
+      const float ce = (px.ms - px.sy) + logf(px.zs);
+      const double wd = (double)wv, wce = (double)wv * (double)ce;
+      const bool cm = 1.f / px.zt > thr;
+      nw += wd;
+      if (cm) scm += wd;
+      // 'pixel': selected, not multiplied -- an unconfident pixel's inf / NaN ce stays out of S_conf
+      if (cm || weighting != 0) sce += wce;
+    }
+  }
+  // the three sums through one pair of barriers
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  nw = wave_sum(nw);
+  scm = wave_sum(scm);
+  sce = wave_sum(sce);
+  if (lane == 0) {
+    red[0][wid] = nw;
+    red[1][wid] = scm;
+    red[2][wid] = sce;
+  }
+  __syncthreads();
+  if (threadIdx.x < CE_SUMS) {
+    double v = 0.0;
+    for (int i = 0; i < SM_TILE / 64; ++i) v += red[threadIdx.x][i];
+    part[(int64_t)CE_SUMS * blockIdx.x + threadIdx.x] = v;
+  }
+}
+
+__global__ void __launch_bounds__(RED_THREADS) cons_ce_final_kernel(const double* __restrict__ part, int nparts,
+                                                                    int64_t npix, int weighting,
+                                                                    float* __restrict__ out4) {
+  __shared__ double red[RED_THREADS / 64];
+  double acc[CE_SUMS] = {0.0, 0.0, 0.0};
+  for (int i = threadIdx.x; i < nparts; i += blockDim.x)
+#pragma unroll
+    for (int k = 0; k < CE_SUMS; ++k) acc[k] += part[(int64_t)CE_SUMS * i + k];
+#pragma unroll
+  for (int k = 0; k < CE_SUMS; ++k) acc[k] = block_sum(acc[k], red);
+  if (threadIdx.x == 0) {
+    const double nw = acc[0], scm = acc[1];
+    // 'pixel': S_conf / N_w (exactly 0 when no pixel is confident);  'batch': (S_cm / N_w) (S_all / N_w);  N_w == 0: NaN
+    out4[0] = (float)(weighting == 0 ? acc[2] / nw : (scm / nw) * (acc[2] / nw));
+    out4[1] = (float)(scm / (double)npix);
+    out4[2] = (float)scm;
+    out4[3] = (float)nw;
+  }
+}
+
+// gs_c = gout k (softmax(s)_c - [c == y]);  'pixel': k = w cm / N_w, exact zeros where cm == 0 (selected: the student's
+// row may be inf / NaN there);  'batch': k = (S_cm / N_w) w / N_w at every pixel
+template <int CMAX>
+__global__ void __launch_bounds__(SM_TILE) cons_ce_bwd_kernel(const float* __restrict__ s,
+                                                              const float* __restrict__ t,
+                                                              const float* __restrict__ w, int C, int64_t HW,
+                                                              int64_t tiles_per_sample, int64_t ntiles, float thr,
+                                                              int weighting, const float* __restrict__ out4,
+                                                              const float* __restrict__ gout,
+                                                              float* __restrict__ gs) {
+  constexpr int K = CMAX < 8 ? CMAX : 8;   // the forward's chunk for this C
+  const float scale = weighting == 0 ? gout[0] / out4[3] : gout[0] * (out4[2] / out4[3]) / out4[3];
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t b = tile / tiles_per_sample;
+    const int64_t pix = (tile - b * tiles_per_sample) * SM_TILE + threadIdx.x;
+    if (pix >= HW) continue;
+    const int64_t base = b * C * HW + pix;
+    const float* sp = s + base;
+    const float* tp = t + base;
+    float ps[CMAX];
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c) ps[c] = sp[(int64_t)(c < C ? c : 0) * HW];
+    const float wv = w ? w[b * HW + pix] : 1.f;
+    float mt = 0.f, zt = 1.f, best = 0.f, pick = 0.f;
+    int arg = 0;
+    {
+      float tv[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k) tv[k] = tp[(int64_t)(k < C ? k : 0) * HW];
+      ce_argmax<K, true>(best, arg, pick, tv, tv, 0, C);
+      if (weighting == 0) ce_absorb<K, true, true>(mt, zt, tv, 0, C);
+    }
+#pragma unroll
+    for (int c0 = K; c0 < CMAX; c0 += K) {
+      if (c0 < C) {
+        float tv[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) tv[k] = tp[(int64_t)(c0 + k < C ? c0 + k : c0) * HW];
+        ce_argmax<K, false>(best, arg, pick, tv, tv, c0, C);
+        if (weighting == 0) ce_absorb<K, false, true>(mt, zt, tv, c0, C);
+      }
+    }
+    const bool on = weighting != 0 || 1.f / zt > thr;
+    float ms = ps[0];
+#pragma unroll
+    for (int c = 1; c < CMAX; ++c)
+      if (c < C) ms = fmaxf(ms, ps[c]);
+    float zs = 0.f;
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c) {
+      ps[c] = c < C ? expf(ps[c] - ms) : 0.f;
+      zs += ps[c];
+    }
+    const float rs = 1.f / zs, k = wv * scale;
+    float* gp = gs + base;
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c)
+      if (c < C) gp[(int64_t)c * HW] = on ? k * (ps[c] * rs - (c == arg ? 1.f : 0.f)) : 0.f;
   }
 }
 
@@ -339,6 +537,21 @@ void launch_sm_bwd(int nb, hipStream_t st, const float* s, const float* t, const
                      out3, gout, gs);
 }
 
+template <int K>
+void launch_ce_fwd(int nb, hipStream_t st, const float* s, const float* t, const float* w, int C, int64_t HW,
+                   int64_t tps, int64_t ntiles, float thr, int weighting, double* part) {
+  hipLaunchKernelGGL(cons_ce_partial_kernel<K>, dim3(nb), dim3(SM_TILE), 0, st, s, t, w, C, HW, tps, ntiles, thr,
+                     weighting, part);
+}
+
+template <int CMAX>
+void launch_ce_bwd(int nb, hipStream_t st, const float* s, const float* t, const float* w, int C, int64_t HW,
+                   int64_t tps, int64_t ntiles, float thr, int weighting, const float* out4, const float* gout,
+                   float* gs) {
+  hipLaunchKernelGGL(cons_ce_bwd_kernel<CMAX>, dim3(nb), dim3(SM_TILE), 0, st, s, t, w, C, HW, tps, ntiles, thr,
+                     weighting, out4, gout, gs);
+}
+
 // the channel bucket of C: the smallest of 2, 4, 8, 16, 32, 64 that holds it
 #define SM_DISPATCH(C, CALL)      \
   do {                            \
@@ -384,6 +597,43 @@ extern "C" int ssseg_consistency_sm_bwd(const float* s, const float* t, const fl
 #define SM_BWD(N) launch_sm_bwd<N>(nb, st, s, t, w, (int)C, HW, tps, ntiles, thr, out3, gout, gs)
   SM_DISPATCH(C, SM_BWD);
 #undef SM_BWD
+  SSSEG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" size_t ssseg_consistency_ce_workspace_bytes(int64_t) { return sizeof(double) * CE_SUMS * RED_BLOCKS; }
+
+extern "C" int ssseg_consistency_ce_fwd(const float* s, const float* t, const float* w, int64_t B, int64_t C,
+                                        int64_t HW, float thr, int weighting, float* out4, void* ws, size_t ws_bytes,
+                                        ssseg_stream_t stream) {
+  if (!s || !t || !out4 || !sm_args_ok(B, C, HW) || (weighting != 0 && weighting != 1)) return SSSEG_EINVAL;
+  if (!ws || ws_bytes < sizeof(double) * CE_SUMS * RED_BLOCKS) return SSSEG_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t tps = (HW + SM_TILE - 1) / SM_TILE, ntiles = B * tps;
+  const int nb = (int)(ntiles < RED_BLOCKS ? ntiles : RED_BLOCKS);
+  // the chunk of the streaming pass: the channel bucket up to 8
+#define CE_FWD(N) launch_ce_fwd<N>(nb, st, s, t, w, (int)C, HW, tps, ntiles, thr, weighting, (double*)ws)
+  if (C <= 2) CE_FWD(2);
+  else if (C <= 4) CE_FWD(4);
+  else CE_FWD(8);
+#undef CE_FWD
+  hipLaunchKernelGGL(cons_ce_final_kernel, dim3(1), dim3(RED_THREADS), 0, st, (const double*)ws, nb, B * HW, weighting,
+                     out4);
+  SSSEG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ssseg_consistency_ce_bwd(const float* s, const float* t, const float* w, int64_t B, int64_t C,
+                                        int64_t HW, float thr, int weighting, const float* out4, const float* gout,
+                                        float* gs, ssseg_stream_t stream) {
+  if (!s || !t || !out4 || !gout || !gs || !sm_args_ok(B, C, HW) || (weighting != 0 && weighting != 1))
+    return SSSEG_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t tps = (HW + SM_TILE - 1) / SM_TILE, ntiles = B * tps;
+  const int nb = (int)(ntiles < SM_BWD_BLOCKS ? ntiles : SM_BWD_BLOCKS);
+#define CE_BWD(N) launch_ce_bwd<N>(nb, st, s, t, w, (int)C, HW, tps, ntiles, thr, weighting, out4, gout, gs)
+  SM_DISPATCH(C, CE_BWD);
+#undef CE_BWD
   SSSEG_LAUNCH_CHECK();
   return 0;
 }

@@ -71,6 +71,9 @@ SIGS = {
     'ssseg_consistency_w_bwd': (i32, [vp, vp, vp, i64, i64, i64, f32, vp, vp, vp, vp]),
     'ssseg_consistency_sm_fwd': (i32, [vp, vp, vp, i64, i64, i64, f32, vp, vp, sz, vp]),
     'ssseg_consistency_sm_bwd': (i32, [vp, vp, vp, i64, i64, i64, f32, vp, vp, vp, vp]),
+    'ssseg_consistency_ce_workspace_bytes': (sz, [i64]),
+    'ssseg_consistency_ce_fwd': (i32, [vp, vp, vp, i64, i64, i64, f32, i32, vp, vp, sz, vp]),
+    'ssseg_consistency_ce_bwd': (i32, [vp, vp, vp, i64, i64, i64, f32, i32, vp, vp, vp, vp]),
     'ssseg_lovasz_workspace_bytes': (sz, [i64, i64]),
     'ssseg_lovasz_fwd': (i32, [vp, vp, i64, i64, i64, vp, vp, sz, vp]),
     'ssseg_lovasz_bwd': (i32, [vp, vp, i64, i64, i64, vp, vp, vp, sz, vp]),

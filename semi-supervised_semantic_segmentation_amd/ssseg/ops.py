@@ -440,6 +440,65 @@ def consistency_loss_softmax(student_logits, teacher_logits, thr, w=None):
     return _ConsistencySoftmax.apply(s, t, thr, w)
 
 
+CE_WEIGHTINGS = {'pixel': 0, 'batch': 1}
+
+
+class _ConsistencyCE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, s, t, thr, w, weighting):
+        s, t = _c(s.float()), _c(t.float())
+        B, C = s.shape[:2]
+        HW = s[0, 0].numel()
+        out = torch.empty(4, device=s.device, dtype=torch.float32)
+        nb = N.lib().ssseg_consistency_ce_workspace_bytes(B * HW)
+        ws = N.workspace(nb, s.device)
+        if w is not None:
+            w = _c(w.float())
+        N.call('ssseg_consistency_ce_fwd', N.dev_ptr(s, 'student'), N.dev_ptr(t, 'teacher'), N.dev_ptr(w, 'w'), B, C,
+               HW, float(thr), weighting, N.dev_ptr(out), N.dev_ptr(ws), nb, N.stream())
+        if w is None:
+            ctx.save_for_backward(s, t, out)
+        else:
+            ctx.save_for_backward(s, t, out, w)
+        ctx.meta = (B, C, HW, float(thr), weighting)
+        loss, cm = out[0], out[1]
+        ctx.mark_non_differentiable(cm)
+        ctx.set_materialize_grads(False)   # no zero-filled gradient for the cm output (a framework fill kernel)
+        return loss, cm
+
+    @staticmethod
+    def backward(ctx, g_loss, g_cm):
+        s, t, out = ctx.saved_tensors[:3]
+        w = ctx.saved_tensors[3] if len(ctx.saved_tensors) > 3 else None
+        B, C, HW, thr, weighting = ctx.meta
+        gs = torch.empty_like(s)
+        g = _c(g_loss.float())
+        N.call('ssseg_consistency_ce_bwd', N.dev_ptr(s), N.dev_ptr(t), N.dev_ptr(w), B, C, HW, thr, weighting,
+               N.dev_ptr(out), N.dev_ptr(g), N.dev_ptr(gs), N.stream())
+        return gs, None, None, None, None
+
+
+def consistency_loss_ce(student_logits, teacher_logits, thr, w=None, weighting='pixel'):
+    """Pseudo-label consistency: cross-entropy of the student against the teacher's hard label y = argmax_c t_c,
+    weighted by the teacher's confidence cm = [max_c softmax(t) > thr] (the teacher gets no gradient).  [B,C,H,W]
+    logits, 1 <= C <= 64; w [B,H,W] (optional, a constant) weighs the pixels.
+    weighting='pixel' (FixMatch, CutMix-Seg): sum(w cm ce) / sum(w), the unconfident pixels selected out -- exactly 0.0,
+    not NaN, when no pixel is confident;  'batch' (ClassMix): (sum(w cm) / sum(w)) * (sum(w ce) / sum(w)), the
+    confident fraction a constant.  Returns (loss, sum(w cm) / npix); the loss is NaN only when sum(w) == 0."""
+    s, t = student_logits, teacher_logits
+    if weighting not in CE_WEIGHTINGS:
+        raise ValueError(f"consistency_loss_ce: weighting must be 'pixel' or 'batch', got {weighting!r}")
+    if s.dim() < 3 or tuple(s.shape) != tuple(t.shape):
+        raise ValueError(f'consistency_loss_ce: student and teacher logits must have one shape [B,C,H,W], got '
+                         f'{tuple(s.shape)} and {tuple(t.shape)}')
+    if s.shape[1] > 64:
+        raise ValueError(f'consistency_loss_ce: {s.shape[1]} channels (at most 64 are supported)')
+    if w is not None and w.numel() != s.shape[0] * s[0, 0].numel():
+        raise ValueError('consistency_loss_ce: w must hold one weight per pixel, [B, H, W]')
+    _device_checked('consistency_loss_ce', student=s, teacher=t, w=w)
+    return _ConsistencyCE.apply(s, t, thr, w, CE_WEIGHTINGS[weighting])
+
+
 # ------------------------------------------------------------------------------------------------
 # EMA / optimiser over flat arenas
 # ------------------------------------------------------------------------------------------------

@@ -176,6 +176,25 @@ def _consistency_activation(tc):
     return activation
 
 
+def _consistency_loss_kind(tc):
+    """config['train']['consistency_loss']: 'mse' (the reference's squared difference of probabilities, and the default)
+    or 'ce' (cross-entropy against the teacher's hard pseudo-label, weighted by its confidence: FixMatch, ClassMix,
+    CutMix-Seg), with config['train']['consistency_ce_weighting'] 'pixel' (the default) or 'batch'.
+    Returns (kind, weighting); the weighting is None under 'mse', which does not use it."""
+    kind = tc.get('consistency_loss', 'mse')
+    if kind not in ('mse', 'ce'):
+        raise ValueError(f"consistency_loss must be 'mse' or 'ce', got {kind!r}")
+    weighting = tc.get('consistency_ce_weighting', 'pixel')
+    if weighting not in ('pixel', 'batch'):
+        raise ValueError(f"consistency_ce_weighting must be 'pixel' or 'batch', got {weighting!r}")
+    if kind == 'mse':
+        return kind, None
+    if _consistency_activation(tc) != 'softmax':
+        raise ValueError("consistency_loss 'ce' is defined over mutually exclusive classes: it needs "
+                         "consistency_activation 'softmax'")
+    return kind, weighting
+
+
 def _consistency_forward(model, targets, tc, epoch):
     """train.py:87-112: the student's eval-mode forward on the mixed images (with grad), resized, and the weighted
     consistency loss.  Returns (unsup_loss, cm_mean)."""
@@ -192,7 +211,13 @@ def _consistency_forward(model, targets, tc, epoch):
     activation = _consistency_activation(tc)
     if aug is not None:
         student_pred = aug.reverse([student_pred])[0]
-    if activation == 'softmax':
+    loss_kind, weighting = _consistency_loss_kind(tc)
+    if loss_kind == 'ce':
+        # the student against the teacher's hard pseudo-label, weighted by the teacher's confidence; no confident pixel
+        # gives 0.0 under 'pixel', where the squared-difference forms below give 0/0
+        consistency, cm_mean = ops.consistency_loss_ce(student_pred, mixed_ema_pred, tc['confidence_threshold'],
+                                                       aug.valid if aug is not None else None, weighting)
+    elif activation == 'softmax':
         # mutually exclusive classes (the reference's commented alternative, train.py:97,99): one softmax over the
         # channels, so that max_c p is a class confidence and confidence_threshold means what it says at any C
         consistency, cm_mean = ops.consistency_loss_softmax(student_pred, mixed_ema_pred, tc['confidence_threshold'],
@@ -234,6 +259,7 @@ def train_step(model, ema_model, optimizer, image, mask, unsup_a, unsup_b, epoch
     adv = tc.get('adversarial')
     if semi:
         mixmasks.mix_mask_kind(tc)   # an unknown mask is refused before anything is launched
+        _consistency_loss_kind(tc)   # and an unknown consistency loss, or 'ce' without the softmax
     features, pred_maps = model(image)
     classification_loss = tc['loss'](pred_maps, mask)
     sup_loss = classification_loss
@@ -343,7 +369,7 @@ def train_step(model, ema_model, optimizer, image, mask, unsup_a, unsup_b, epoch
 # the benchmark: C5 (HarDNet + discriminator, ~660 small launches) 63.6 -> 33.5 ms/step, C4 213 -> 195 ms.  A replay
 # repeats the Python decisions of its capture, so the graph is keyed on every one of them: the optimizer step taken
 # or skipped (train.py:121, step % virtual_batch_size_multiplier), the epoch gate of the consistency weight
-# (train.py:112), the consistency activation, the mixing mask, every learning rate, the input geometry and compute dtype -- a new key
+# (train.py:112), the consistency activation, loss and weighting, the mixing mask, every learning rate, the input geometry and compute dtype -- a new key
 # captures a new graph (the two
 # most recent are kept).  Not captured (eager steps instead): CowMix drawn from the CPU generator (parity mode),
 # ClassMix / CutMix draws from the host generator or fixed (mixmasks.DRAW_SOURCE, set_draws), a
@@ -394,7 +420,7 @@ def _graph_key(model, ema_model, optimizer, image, mask, unsup_a, unsup_b, epoch
     lrs = tuple(float(g['lr']) for o in opts for g in o.param_groups)
     shapes = tuple((tuple(t.shape), t.dtype) if t is not None else None for t in (image, mask, unsup_a, unsup_b))
     return step_key + (id(optimizer), opt_step, float(epoch > 25), lrs, shapes, id(config),
-                       _consistency_activation(tc), kind)
+                       _consistency_activation(tc), kind) + _consistency_loss_kind(tc)
 
 
 def _graph_step(key, model, ema_model, optimizer, image, mask, unsup_a, unsup_b, epoch, step, config):

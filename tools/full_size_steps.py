@@ -31,12 +31,13 @@ import torch.distributed as dist  # noqa: E402
 # semi-supervised step GFLOP per labelled image (3F sup fwd+bwd + 2F teacher + 3F consistency fwd+bwd)
 # (c2geo: the same convs; c6: C2's convs with a 19-class head, +0.1 %)
 STEP_GFLOP_PER_IMAGE = {'c2': 765.1, 'c2geo': 765.1, 'c2cutmix': 765.1, 'c3': 3855.8, 'c4': 3904.2, 'c5': 85.2, 'c6': 765.1,
-                        'c6classmix': 765.1}
+                        'c6classmix': 765.1, 'c6classmixce': 765.1, 'c6cutmixce': 765.1}
 PEAK = {'bfloat16': 2.5e15, 'float16': 2.5e15, 'float32': 0.16e15}   # dense MFMA (MI355X_MICROARCH.md)
 CFGS = {'c2': 'configs/c2_unet_r50.py', 'c2geo': 'configs/c2_unet_r50_geo.py', 'c3': 'configs/c3_deeplabv3_r101.py',
         'c4': 'configs/c4_msa_hrnet.py', 'c5': 'configs/c5_hardnet_disc.py',
         'c6': 'configs/c6_unet_r50_multiclass.py', 'c6classmix': 'configs/c6_unet_r50_classmix.py',
-        'c2cutmix': 'configs/c2_unet_r50_cutmix.py'}
+        'c2cutmix': 'configs/c2_unet_r50_cutmix.py', 'c6classmixce': 'configs/c6_unet_r50_classmix_ce.py',
+        'c6cutmixce': 'configs/c6_unet_r50_cutmix_ce.py'}
 MIX_MASK = {'kind': None}   # --mix-mask: the mixing mask of every config of the run (train['mix_mask'])
 
 
