@@ -281,6 +281,29 @@ int ssseg_consistency_ce_fwd(const float* s, const float* t, const float* w, int
 int ssseg_consistency_ce_bwd(const float* s, const float* t, const float* w, int64_t B, int64_t C, int64_t HW,
                              float thr, int weighting, const float* out4, const float* gout, float* gs,
                              ssseg_stream_t stream);
+/* The same two passes with one threshold per class: thr_c (device, C floats) in the place of thr, the decision
+ * cm = [conf > thr_c[y]] at the teacher's label y, from the same bits in both passes ('batch': the backward does not
+ * read thr_c).  thr_c == NULL is SSSEG_EINVAL.  Everything else -- operands, out4, workspace, both weightings, w -- is
+ * the scalar entry points'; thr_c filled with one value gives their results bit for bit. */
+int ssseg_consistency_ce_cls_fwd(const float* s, const float* t, const float* w, int64_t B, int64_t C, int64_t HW,
+                                 const float* thr_c, int weighting, float* out4, void* ws, size_t ws_bytes,
+                                 ssseg_stream_t stream);
+int ssseg_consistency_ce_cls_bwd(const float* s, const float* t, const float* w, int64_t B, int64_t C, int64_t HW,
+                                 const float* thr_c, int weighting, const float* out4, const float* gout, float* gs,
+                                 ssseg_stream_t stream);
+/* Self-adaptive per-class confidence thresholds (csrc/adaptive_thr.hip; FreeMatch, Wang et al. 2023, eqs. 5-8).  One
+ * pass over the teacher's logits t [B,C,HW] f32 contiguous, 1 <= C <= 64, then the update of the device state in place:
+ *   p = softmax_c(t) per pixel (fp32, maximum subtracted),  m = mean_pix max_c p,  q_c = mean_pix p_c,
+ *   tau <- momentum tau + (1 - momentum) m,  ptilde_c <- momentum ptilde_c + (1 - momentum) q_c        (fp64),
+ *   thr_c[c] = (float)((ptilde_c / max_k ptilde_k) tau).
+ * state: 2 C + 3 doubles on the device: [0] tau, [1, C] ptilde, [C + 1] the number of updates, [C + 2] the last m,
+ * [C + 3, 2 C + 2] the last q_c (written, never read); the caller initialises tau = ptilde_c = 1 / C and the count 0.
+ * thr_c: C floats, overwritten.  Refused before any launch: null t / state / thr_c, C outside [1, 64], B or HW <= 0,
+ * momentum outside [0, 1) (SSSEG_EINVAL); ws NULL or shorter than ssseg_adaptive_thr_workspace_bytes(C)
+ * (SSSEG_EWORKSPACE; (C + 1) fp64 partials per workgroup).  Bitwise reproducible; graph-capturable. */
+size_t ssseg_adaptive_thr_workspace_bytes(int64_t C);
+int ssseg_adaptive_thr_update(const float* t, int64_t B, int64_t C, int64_t HW, double momentum, double* state,
+                              float* thr_c, void* ws, size_t ws_bytes, ssseg_stream_t stream);
 
 /* Binary Lovász (losses.binary_lovasz_loss_with_logits losses.py:239-250 -> lovasz_softmax
  * lovasz.py:155-201 with classes=[1], per_image=True).  logits, target [B,C,HW] f32, 1 <= B <= 4096.

@@ -222,12 +222,16 @@ struct CePixel {
   }
 };
 
-template <int K>
+// CLS: the threshold is per class, thr_c[y] (device, C floats: the self-adaptive thresholds of adaptive_thr.hip), in the
+// place of the scalar thr -- one indexed load per pixel, y always inside [0, C); the scalar instantiations do not
+// touch thr_c
+template <int K, bool CLS>
 __global__ void __launch_bounds__(SM_TILE) cons_ce_partial_kernel(const float* __restrict__ s,
                                                                   const float* __restrict__ t,
                                                                   const float* __restrict__ w, int C, int64_t HW,
                                                                   int64_t tiles_per_sample, int64_t ntiles, float thr,
-                                                                  int weighting, double* __restrict__ part) {
+                                                                  const float* __restrict__ thr_c, int weighting,
+                                                                  double* __restrict__ part) {
   __shared__ double red[CE_SUMS][SM_TILE / 64];
   double nw = 0.0, scm = 0.0, sce = 0.0;
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
@@ -242,7 +246,7 @@ __global__ void __launch_bounds__(SM_TILE) cons_ce_partial_kernel(const float* _
       for (int c0 = K; c0 < C; c0 += K) px.chunk<K, false>(sp, tp, c0, C, HW);
       const float ce = (px.ms - px.sy) + logf(px.zs);
       const double wd = (double)wv, wce = (double)wv * (double)ce;
-      const bool cm = 1.f / px.zt > thr;
+      const bool cm = 1.f / px.zt > (CLS ? thr_c[px.arg] : thr);
       nw += wd;
       if (cm) scm += wd;
       // 'pixel': selected, not multiplied -- an unconfident pixel's inf / NaN ce stays out of S_conf
@@ -289,12 +293,13 @@ __global__ void __launch_bounds__(RED_THREADS) cons_ce_final_kernel(const double
 
 // gs_c = gout k (softmax(s)_c - [c == y]);  'pixel': k = w cm / N_w, exact zeros where cm == 0 (selected: the student's
 // row may be inf / NaN there);  'batch': k = (S_cm / N_w) w / N_w at every pixel
-template <int CMAX>
+template <int CMAX, bool CLS>
 __global__ void __launch_bounds__(SM_TILE) cons_ce_bwd_kernel(const float* __restrict__ s,
                                                               const float* __restrict__ t,
                                                               const float* __restrict__ w, int C, int64_t HW,
                                                               int64_t tiles_per_sample, int64_t ntiles, float thr,
-                                                              int weighting, const float* __restrict__ out4,
+                                                              const float* __restrict__ thr_c, int weighting,
+                                                              const float* __restrict__ out4,
                                                               const float* __restrict__ gout,
                                                               float* __restrict__ gs) {
   constexpr int K = CMAX < 8 ? CMAX : 8;   // the forward's chunk for this C
@@ -329,7 +334,7 @@ __global__ void __launch_bounds__(SM_TILE) cons_ce_bwd_kernel(const float* __res
         if (weighting == 0) ce_absorb<K, false, true>(mt, zt, tv, c0, C);
       }
     }
-    const bool on = weighting != 0 || 1.f / zt > thr;
+    const bool on = weighting != 0 || 1.f / zt > (CLS ? thr_c[arg] : thr);
     float ms = ps[0];
 #pragma unroll
     for (int c = 1; c < CMAX; ++c)
@@ -537,19 +542,28 @@ void launch_sm_bwd(int nb, hipStream_t st, const float* s, const float* t, const
                      out3, gout, gs);
 }
 
+// thr_c == nullptr: the scalar threshold thr;  else the per-class thresholds (thr is not read)
 template <int K>
 void launch_ce_fwd(int nb, hipStream_t st, const float* s, const float* t, const float* w, int C, int64_t HW,
-                   int64_t tps, int64_t ntiles, float thr, int weighting, double* part) {
-  hipLaunchKernelGGL(cons_ce_partial_kernel<K>, dim3(nb), dim3(SM_TILE), 0, st, s, t, w, C, HW, tps, ntiles, thr,
-                     weighting, part);
+                   int64_t tps, int64_t ntiles, float thr, const float* thr_c, int weighting, double* part) {
+  if (thr_c)
+    hipLaunchKernelGGL((cons_ce_partial_kernel<K, true>), dim3(nb), dim3(SM_TILE), 0, st, s, t, w, C, HW, tps, ntiles,
+                       thr, thr_c, weighting, part);
+  else
+    hipLaunchKernelGGL((cons_ce_partial_kernel<K, false>), dim3(nb), dim3(SM_TILE), 0, st, s, t, w, C, HW, tps, ntiles,
+                       thr, thr_c, weighting, part);
 }
 
 template <int CMAX>
 void launch_ce_bwd(int nb, hipStream_t st, const float* s, const float* t, const float* w, int C, int64_t HW,
-                   int64_t tps, int64_t ntiles, float thr, int weighting, const float* out4, const float* gout,
-                   float* gs) {
-  hipLaunchKernelGGL(cons_ce_bwd_kernel<CMAX>, dim3(nb), dim3(SM_TILE), 0, st, s, t, w, C, HW, tps, ntiles, thr,
-                     weighting, out4, gout, gs);
+                   int64_t tps, int64_t ntiles, float thr, const float* thr_c, int weighting, const float* out4,
+                   const float* gout, float* gs) {
+  if (thr_c)
+    hipLaunchKernelGGL((cons_ce_bwd_kernel<CMAX, true>), dim3(nb), dim3(SM_TILE), 0, st, s, t, w, C, HW, tps, ntiles,
+                       thr, thr_c, weighting, out4, gout, gs);
+  else
+    hipLaunchKernelGGL((cons_ce_bwd_kernel<CMAX, false>), dim3(nb), dim3(SM_TILE), 0, st, s, t, w, C, HW, tps, ntiles,
+                       thr, thr_c, weighting, out4, gout, gs);
 }
 
 // the channel bucket of C: the smallest of 2, 4, 8, 16, 32, 64 that holds it
@@ -603,16 +617,16 @@ extern "C" int ssseg_consistency_sm_bwd(const float* s, const float* t, const fl
 
 extern "C" size_t ssseg_consistency_ce_workspace_bytes(int64_t) { return sizeof(double) * CE_SUMS * RED_BLOCKS; }
 
-extern "C" int ssseg_consistency_ce_fwd(const float* s, const float* t, const float* w, int64_t B, int64_t C,
-                                        int64_t HW, float thr, int weighting, float* out4, void* ws, size_t ws_bytes,
-                                        ssseg_stream_t stream) {
+// both threshold forms of the two entry points: thr_c == nullptr is the scalar one
+static int ce_fwd(const float* s, const float* t, const float* w, int64_t B, int64_t C, int64_t HW, float thr,
+                  const float* thr_c, int weighting, float* out4, void* ws, size_t ws_bytes, ssseg_stream_t stream) {
   if (!s || !t || !out4 || !sm_args_ok(B, C, HW) || (weighting != 0 && weighting != 1)) return SSSEG_EINVAL;
   if (!ws || ws_bytes < sizeof(double) * CE_SUMS * RED_BLOCKS) return SSSEG_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const int64_t tps = (HW + SM_TILE - 1) / SM_TILE, ntiles = B * tps;
   const int nb = (int)(ntiles < RED_BLOCKS ? ntiles : RED_BLOCKS);
   // the chunk of the streaming pass: the channel bucket up to 8
-#define CE_FWD(N) launch_ce_fwd<N>(nb, st, s, t, w, (int)C, HW, tps, ntiles, thr, weighting, (double*)ws)
+#define CE_FWD(N) launch_ce_fwd<N>(nb, st, s, t, w, (int)C, HW, tps, ntiles, thr, thr_c, weighting, (double*)ws)
   if (C <= 2) CE_FWD(2);
   else if (C <= 4) CE_FWD(4);
   else CE_FWD(8);
@@ -623,19 +637,45 @@ extern "C" int ssseg_consistency_ce_fwd(const float* s, const float* t, const fl
   return 0;
 }
 
-extern "C" int ssseg_consistency_ce_bwd(const float* s, const float* t, const float* w, int64_t B, int64_t C,
-                                        int64_t HW, float thr, int weighting, const float* out4, const float* gout,
-                                        float* gs, ssseg_stream_t stream) {
+static int ce_bwd(const float* s, const float* t, const float* w, int64_t B, int64_t C, int64_t HW, float thr,
+                  const float* thr_c, int weighting, const float* out4, const float* gout, float* gs,
+                  ssseg_stream_t stream) {
   if (!s || !t || !out4 || !gout || !gs || !sm_args_ok(B, C, HW) || (weighting != 0 && weighting != 1))
     return SSSEG_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   const int64_t tps = (HW + SM_TILE - 1) / SM_TILE, ntiles = B * tps;
   const int nb = (int)(ntiles < SM_BWD_BLOCKS ? ntiles : SM_BWD_BLOCKS);
-#define CE_BWD(N) launch_ce_bwd<N>(nb, st, s, t, w, (int)C, HW, tps, ntiles, thr, weighting, out4, gout, gs)
+#define CE_BWD(N) launch_ce_bwd<N>(nb, st, s, t, w, (int)C, HW, tps, ntiles, thr, thr_c, weighting, out4, gout, gs)
   SM_DISPATCH(C, CE_BWD);
 #undef CE_BWD
   SSSEG_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int ssseg_consistency_ce_fwd(const float* s, const float* t, const float* w, int64_t B, int64_t C,
+                                        int64_t HW, float thr, int weighting, float* out4, void* ws, size_t ws_bytes,
+                                        ssseg_stream_t stream) {
+  return ce_fwd(s, t, w, B, C, HW, thr, nullptr, weighting, out4, ws, ws_bytes, stream);
+}
+
+extern "C" int ssseg_consistency_ce_bwd(const float* s, const float* t, const float* w, int64_t B, int64_t C,
+                                        int64_t HW, float thr, int weighting, const float* out4, const float* gout,
+                                        float* gs, ssseg_stream_t stream) {
+  return ce_bwd(s, t, w, B, C, HW, thr, nullptr, weighting, out4, gout, gs, stream);
+}
+
+extern "C" int ssseg_consistency_ce_cls_fwd(const float* s, const float* t, const float* w, int64_t B, int64_t C,
+                                            int64_t HW, const float* thr_c, int weighting, float* out4, void* ws,
+                                            size_t ws_bytes, ssseg_stream_t stream) {
+  if (!thr_c) return SSSEG_EINVAL;
+  return ce_fwd(s, t, w, B, C, HW, 0.f, thr_c, weighting, out4, ws, ws_bytes, stream);
+}
+
+extern "C" int ssseg_consistency_ce_cls_bwd(const float* s, const float* t, const float* w, int64_t B, int64_t C,
+                                            int64_t HW, const float* thr_c, int weighting, const float* out4,
+                                            const float* gout, float* gs, ssseg_stream_t stream) {
+  if (!thr_c) return SSSEG_EINVAL;
+  return ce_bwd(s, t, w, B, C, HW, 0.f, thr_c, weighting, out4, gout, gs, stream);
 }
 
 extern "C" int ssseg_seg_metrics_mc(const float* logits, const int64_t* lstride, int64_t h, int64_t w,

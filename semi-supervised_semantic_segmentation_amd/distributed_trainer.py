@@ -103,6 +103,11 @@ def distributed_train(rank, cfg_path):
             cfg['train']['adversarial']['optimizer'].load_state_dict(ck['discriminator_optimizer'])
             _load_scaler_state(cfg['train']['adversarial']['optimizer'], ck.get('discriminator_grad_scaler'))
             snn.invalidate_packed(disc.module)
+        sat = train._adaptive_threshold(cfg['train'])
+        if sat is not None and 'confidence_threshold_state' in ck:
+            # rank 0's thresholds for every rank (the states are per rank and the checkpoint holds rank 0's); a
+            # checkpoint without the key starts them at 1 / C
+            sat.load_state_dict(ck['confidence_threshold_state'])
         best_metric, last_epoch = ck['best_metric'], ck['epoch']
         snn.invalidate_packed(model.module)
         snn.invalidate_packed(ema_model)
@@ -150,6 +155,9 @@ def distributed_train(rank, cfg_path):
                 ck['discriminator_optimizer'] = cfg['train']['adversarial']['optimizer'].state_dict()
                 if fp16:
                     ck['discriminator_grad_scaler'] = _scaler_state(cfg['train']['adversarial']['optimizer'])
+            sat = train._adaptive_threshold(tc)
+            if sat is not None:   # an extra key, only under confidence_threshold_mode 'adaptive'
+                ck['confidence_threshold_state'] = sat.state_dict()
             torch.save(ck, latest)
             if best_metric is None or val_loss < best_metric:
                 best_metric = val_loss

@@ -74,6 +74,10 @@ SIGS = {
     'ssseg_consistency_ce_workspace_bytes': (sz, [i64]),
     'ssseg_consistency_ce_fwd': (i32, [vp, vp, vp, i64, i64, i64, f32, i32, vp, vp, sz, vp]),
     'ssseg_consistency_ce_bwd': (i32, [vp, vp, vp, i64, i64, i64, f32, i32, vp, vp, vp, vp]),
+    'ssseg_consistency_ce_cls_fwd': (i32, [vp, vp, vp, i64, i64, i64, vp, i32, vp, vp, sz, vp]),
+    'ssseg_consistency_ce_cls_bwd': (i32, [vp, vp, vp, i64, i64, i64, vp, i32, vp, vp, vp, vp]),
+    'ssseg_adaptive_thr_workspace_bytes': (sz, [i64]),
+    'ssseg_adaptive_thr_update': (i32, [vp, i64, i64, i64, f64, vp, vp, vp, sz, vp]),
     'ssseg_lovasz_workspace_bytes': (sz, [i64, i64]),
     'ssseg_lovasz_fwd': (i32, [vp, vp, i64, i64, i64, vp, vp, sz, vp]),
     'ssseg_lovasz_bwd': (i32, [vp, vp, i64, i64, i64, vp, vp, vp, sz, vp]),

@@ -454,13 +454,20 @@ class _ConsistencyCE(torch.autograd.Function):
         ws = N.workspace(nb, s.device)
         if w is not None:
             w = _c(w.float())
-        N.call('ssseg_consistency_ce_fwd', N.dev_ptr(s, 'student'), N.dev_ptr(t, 'teacher'), N.dev_ptr(w, 'w'), B, C,
-               HW, float(thr), weighting, N.dev_ptr(out), N.dev_ptr(ws), nb, N.stream())
+        # a [C] device tensor is one threshold per class (the _cls entry points); anything else is the scalar
+        cls = isinstance(thr, torch.Tensor)
+        if cls:
+            N.call('ssseg_consistency_ce_cls_fwd', N.dev_ptr(s, 'student'), N.dev_ptr(t, 'teacher'), N.dev_ptr(w, 'w'),
+                   B, C, HW, N.dev_ptr(thr, 'thr'), weighting, N.dev_ptr(out), N.dev_ptr(ws), nb, N.stream())
+        else:
+            N.call('ssseg_consistency_ce_fwd', N.dev_ptr(s, 'student'), N.dev_ptr(t, 'teacher'), N.dev_ptr(w, 'w'), B,
+                   C, HW, float(thr), weighting, N.dev_ptr(out), N.dev_ptr(ws), nb, N.stream())
         if w is None:
             ctx.save_for_backward(s, t, out)
         else:
             ctx.save_for_backward(s, t, out, w)
-        ctx.meta = (B, C, HW, float(thr), weighting)
+        # (the threshold vector is a constant that is not an output: kept as it is, like the scalar)
+        ctx.meta = (B, C, HW, thr if cls else float(thr), weighting)
         loss, cm = out[0], out[1]
         ctx.mark_non_differentiable(cm)
         ctx.set_materialize_grads(False)   # no zero-filled gradient for the cm output (a framework fill kernel)
@@ -473,15 +480,21 @@ class _ConsistencyCE(torch.autograd.Function):
         B, C, HW, thr, weighting = ctx.meta
         gs = torch.empty_like(s)
         g = _c(g_loss.float())
-        N.call('ssseg_consistency_ce_bwd', N.dev_ptr(s), N.dev_ptr(t), N.dev_ptr(w), B, C, HW, thr, weighting,
-               N.dev_ptr(out), N.dev_ptr(g), N.dev_ptr(gs), N.stream())
+        if isinstance(thr, torch.Tensor):
+            N.call('ssseg_consistency_ce_cls_bwd', N.dev_ptr(s), N.dev_ptr(t), N.dev_ptr(w), B, C, HW, N.dev_ptr(thr),
+                   weighting, N.dev_ptr(out), N.dev_ptr(g), N.dev_ptr(gs), N.stream())
+        else:
+            N.call('ssseg_consistency_ce_bwd', N.dev_ptr(s), N.dev_ptr(t), N.dev_ptr(w), B, C, HW, thr, weighting,
+                   N.dev_ptr(out), N.dev_ptr(g), N.dev_ptr(gs), N.stream())
         return gs, None, None, None, None
 
 
 def consistency_loss_ce(student_logits, teacher_logits, thr, w=None, weighting='pixel'):
     """Pseudo-label consistency: cross-entropy of the student against the teacher's hard label y = argmax_c t_c,
     weighted by the teacher's confidence cm = [max_c softmax(t) > thr] (the teacher gets no gradient).  [B,C,H,W]
-    logits, 1 <= C <= 64; w [B,H,W] (optional, a constant) weighs the pixels.
+    logits, 1 <= C <= 64; w [B,H,W] (optional, a constant) weighs the pixels.  thr is a Python float, or a [C] float32
+    tensor on the logits' device holding one threshold per class, read at the teacher's label: cm = [conf > thr[y]]
+    (AdaptiveThreshold.update returns one; it is read when the kernels run, in the backward pass too).
     weighting='pixel' (FixMatch, CutMix-Seg): sum(w cm ce) / sum(w), the unconfident pixels selected out -- exactly 0.0,
     not NaN, when no pixel is confident;  'batch' (ClassMix): (sum(w cm) / sum(w)) * (sum(w ce) / sum(w)), the
     confident fraction a constant.  Returns (loss, sum(w cm) / npix); the loss is NaN only when sum(w) == 0."""
@@ -495,8 +508,131 @@ def consistency_loss_ce(student_logits, teacher_logits, thr, w=None, weighting='
         raise ValueError(f'consistency_loss_ce: {s.shape[1]} channels (at most 64 are supported)')
     if w is not None and w.numel() != s.shape[0] * s[0, 0].numel():
         raise ValueError('consistency_loss_ce: w must hold one weight per pixel, [B, H, W]')
+    cls = isinstance(thr, torch.Tensor)
+    if cls and (thr.dim() != 1 or thr.numel() != s.shape[1] or thr.dtype != torch.float32 or not thr.is_contiguous()):
+        raise ValueError(f'consistency_loss_ce: a threshold tensor must be a contiguous float32 vector of '
+                         f'{s.shape[1]} entries (one per class), got {tuple(thr.shape)} {thr.dtype}')
     _device_checked('consistency_loss_ce', student=s, teacher=t, w=w)
+    if cls:
+        if thr.device != s.device:
+            raise ValueError(f'consistency_loss_ce: the threshold vector is on {thr.device}, the logits on {s.device}')
+        thr = thr.detach()
     return _ConsistencyCE.apply(s, t, thr, w, CE_WEIGHTINGS[weighting])
+
+
+class AdaptiveThreshold:
+    """Self-adaptive per-class confidence thresholds (FreeMatch: Wang et al., ICLR 2023, section 3.2, eqs. 5-8) for
+    consistency_loss_ce.  The state -- tau, the EMA of the teacher's mean confidence, ptilde[C], the EMA of its class
+    marginals, and the number of updates -- is fp64 on the device and is updated by one kernel sequence per step
+    (ssseg_adaptive_thr_update: no host sync, graph-capturable); tau = ptilde_c = 1 / C at the start.
+    update(teacher_logits) performs  tau <- m tau + (1 - m) mean max_c softmax(t),  ptilde_c <- m ptilde_c + (1 - m)
+    mean softmax(t)_c  over all pixels of the batch and returns thr_c = ptilde_c / max_k ptilde_k * tau as a [C] float32
+    device tensor -- the same storage at every call, overwritten by the next.  The device state is allocated at the
+    first update, from that teacher's C and device: an eager step, before any capture.  Under data parallelism every
+    rank's state follows its own batches (no collective)."""
+
+    def __init__(self, momentum=0.999, num_classes=None):
+        self.momentum = self._checked_momentum(momentum)
+        self.state = self.thr = None           # device: [2 C + 3] fp64 (include/ssseg.h), [C] fp32
+        self._host = None                      # (tau, ptilde, steps) while there is no device state
+        if num_classes is not None:
+            if not 1 <= int(num_classes) <= 64:
+                raise ValueError(f'AdaptiveThreshold: {num_classes} classes (1 to 64 are supported)')
+            self._host = self._initial(int(num_classes))
+
+    @staticmethod
+    def _checked_momentum(momentum):
+        momentum = float(momentum)
+        if not 0.0 <= momentum < 1.0:
+            raise ValueError(f'AdaptiveThreshold: momentum must be in [0, 1), got {momentum!r}')
+        return momentum
+
+    @staticmethod
+    def _initial(C):
+        return 1.0 / C, [1.0 / C] * C, 0
+
+    @property
+    def num_classes(self):
+        if self.thr is not None:
+            return self.thr.numel()
+        return len(self._host[1]) if self._host is not None else None
+
+    def _upload(self, tau, ptilde, steps):
+        C = len(ptilde)
+        host = torch.tensor([tau] + list(ptilde) + [float(steps)] + [0.0] * (C + 1), dtype=torch.float64)
+        self.state.copy_(host)
+        # thr_c of the state as it stands (the rule's expression, in fp64, rounded once)
+        pt = host[1:C + 1]
+        self.thr.copy_(((pt / pt.max()) * host[0]).float())
+
+    def _allocate(self, C, device):
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('AdaptiveThreshold: the first update allocates the state and must run eagerly, '
+                               'before the step is captured')
+        if self._host is not None and len(self._host[1]) != C:
+            raise ValueError(f'AdaptiveThreshold: the state holds {len(self._host[1])} classes, the teacher has {C}')
+        self.state = torch.empty(2 * C + 3, dtype=torch.float64, device=device)
+        self.thr = torch.empty(C, dtype=torch.float32, device=device)
+        self._upload(*(self._host or self._initial(C)))
+        self._host = None
+
+    def update(self, teacher_logits):
+        t = teacher_logits
+        if t.dim() < 3 or not 1 <= t.shape[1] <= 64:
+            raise ValueError(f'AdaptiveThreshold.update: teacher logits must be [B,C,H,W] with 1 <= C <= 64, got '
+                             f'{tuple(t.shape)}')
+        _device_checked('AdaptiveThreshold.update', teacher=t)
+        t = _c(t.detach().float())
+        B, C = t.shape[:2]
+        HW = t[0, 0].numel()
+        if self.state is None:
+            self._allocate(C, t.device)
+        elif self.thr.numel() != C or self.thr.device != t.device:
+            raise ValueError(f'AdaptiveThreshold.update: the state holds {self.thr.numel()} classes on '
+                             f'{self.thr.device}, the teacher has {C} on {t.device}')
+        nb = N.lib().ssseg_adaptive_thr_workspace_bytes(C)
+        ws = N.workspace(nb, t.device)
+        N.call('ssseg_adaptive_thr_update', N.dev_ptr(t, 'teacher'), B, C, HW, self.momentum, N.dev_ptr(self.state),
+               N.dev_ptr(self.thr), N.dev_ptr(ws), nb, N.stream())
+        return self.thr
+
+    def reset(self):
+        """back to tau = ptilde_c = 1 / C and no update taken (the device tensors stay the same storage)"""
+        if self.state is not None:
+            self._upload(*self._initial(self.thr.numel()))
+        elif self._host is not None:
+            self._host = self._initial(len(self._host[1]))
+
+    def tau(self):
+        """the current tau as a Python float (a host sync where the state is on the device: for logging points)"""
+        if self.state is not None:
+            return float(self.state[0])
+        return self._host[0] if self._host is not None else None
+
+    def state_dict(self):
+        """host copies: {'tau': float, 'ptilde': [C floats], 'steps': int} ({} before the class count is known)"""
+        if self.state is not None:
+            C = self.thr.numel()
+            host = self.state[:C + 2].cpu().tolist()
+            return {'tau': host[0], 'ptilde': host[1:C + 1], 'steps': int(host[C + 1])}
+        if self._host is None:
+            return {}
+        return {'tau': self._host[0], 'ptilde': list(self._host[1]), 'steps': self._host[2]}
+
+    def load_state_dict(self, sd):
+        if not sd:
+            return
+        tau, ptilde, steps = float(sd['tau']), [float(v) for v in sd['ptilde']], int(sd['steps'])
+        C = self.num_classes
+        if C is not None and len(ptilde) != C:
+            raise ValueError(f'AdaptiveThreshold.load_state_dict: the state dict holds {len(ptilde)} classes, this '
+                             f'object {C}')
+        if not 1 <= len(ptilde) <= 64:
+            raise ValueError(f'AdaptiveThreshold.load_state_dict: {len(ptilde)} classes (1 to 64 are supported)')
+        if self.state is not None:
+            self._upload(tau, ptilde, steps)
+        else:
+            self._host = (tau, ptilde, steps)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -195,6 +195,45 @@ def _consistency_loss_kind(tc):
     return kind, weighting
 
 
+def _confidence_threshold_mode(tc):
+    """config['train']['confidence_threshold_mode']: 'fixed' (the scalar confidence_threshold, and the default) or
+    'adaptive' (self-adaptive per-class thresholds that follow the teacher, ops.AdaptiveThreshold, with
+    config['train']['confidence_threshold_momentum'], default 0.999; defined for consistency_loss 'ce').
+    Returns (mode, momentum); the momentum is None under 'fixed', which does not use it."""
+    mode = tc.get('confidence_threshold_mode', 'fixed')
+    if mode == 'fixed':
+        return mode, None
+    if mode != 'adaptive':
+        raise ValueError(f"confidence_threshold_mode must be 'fixed' or 'adaptive', got {mode!r}")
+    if _consistency_loss_kind(tc)[0] != 'ce':
+        raise ValueError("confidence_threshold_mode 'adaptive' is defined for consistency_loss 'ce' (the squared-"
+                         "difference forms keep the scalar confidence_threshold)")
+    momentum = tc.get('confidence_threshold_momentum', 0.999)
+    if not isinstance(momentum, (int, float)) or not 0.0 <= momentum < 1.0:
+        raise ValueError(f'confidence_threshold_momentum must be a number in [0, 1), got {momentum!r}')
+    return mode, float(momentum)
+
+
+def _adaptive_threshold(tc):
+    """The ops.AdaptiveThreshold of an 'adaptive' config (None under 'fixed'): created on first use, it takes its place
+    in the config as config['train']['confidence_threshold_state'] (where the trainer finds it for its checkpoints)."""
+    mode, momentum = _confidence_threshold_mode(tc)
+    if mode == 'fixed':
+        return None
+    sat = tc.get('confidence_threshold_state')
+    if sat is None:
+        sat = tc['confidence_threshold_state'] = ops.AdaptiveThreshold(momentum)
+    sat.momentum = momentum
+    return sat
+
+
+def _threshold_key(tc):
+    """The captured step's key components of the threshold: the mode, the momentum (a kernel argument of the capture)
+    and the state object whose device tensors the capture wrote."""
+    sat = _adaptive_threshold(tc)
+    return _confidence_threshold_mode(tc) + (id(sat) if sat is not None else None,)
+
+
 def _consistency_forward(model, targets, tc, epoch):
     """train.py:87-112: the student's eval-mode forward on the mixed images (with grad), resized, and the weighted
     consistency loss.  Returns (unsup_loss, cm_mean)."""
@@ -215,7 +254,12 @@ def _consistency_forward(model, targets, tc, epoch):
     if loss_kind == 'ce':
         # the student against the teacher's hard pseudo-label, weighted by the teacher's confidence; no confident pixel
         # gives 0.0 under 'pixel', where the squared-difference forms below give 0/0
-        consistency, cm_mean = ops.consistency_loss_ce(student_pred, mixed_ema_pred, tc['confidence_threshold'],
+        sat = _adaptive_threshold(tc)
+        # 'adaptive': the thresholds follow the targets the student is trained against -- updated first, on every step
+        # (also those before the epoch gate opens, so that they are warm when it does), and this step's loss reads the
+        # new ones (the published order); aug.valid does not enter them: it says where the student's view left the frame
+        thr = sat.update(mixed_ema_pred) if sat is not None else tc['confidence_threshold']
+        consistency, cm_mean = ops.consistency_loss_ce(student_pred, mixed_ema_pred, thr,
                                                        aug.valid if aug is not None else None, weighting)
     elif activation == 'softmax':
         # mutually exclusive classes (the reference's commented alternative, train.py:97,99): one softmax over the
@@ -260,6 +304,7 @@ def train_step(model, ema_model, optimizer, image, mask, unsup_a, unsup_b, epoch
     if semi:
         mixmasks.mix_mask_kind(tc)   # an unknown mask is refused before anything is launched
         _consistency_loss_kind(tc)   # and an unknown consistency loss, or 'ce' without the softmax
+        _confidence_threshold_mode(tc)   # and an unknown threshold mode, or 'adaptive' without 'ce'
     features, pred_maps = model(image)
     classification_loss = tc['loss'](pred_maps, mask)
     sup_loss = classification_loss
@@ -369,7 +414,8 @@ def train_step(model, ema_model, optimizer, image, mask, unsup_a, unsup_b, epoch
 # the benchmark: C5 (HarDNet + discriminator, ~660 small launches) 63.6 -> 33.5 ms/step, C4 213 -> 195 ms.  A replay
 # repeats the Python decisions of its capture, so the graph is keyed on every one of them: the optimizer step taken
 # or skipped (train.py:121, step % virtual_batch_size_multiplier), the epoch gate of the consistency weight
-# (train.py:112), the consistency activation, loss and weighting, the mixing mask, every learning rate, the input geometry and compute dtype -- a new key
+# (train.py:112), the consistency activation, loss and weighting, the confidence threshold's mode, momentum and state
+# object, the mixing mask, every learning rate, the input geometry and compute dtype -- a new key
 # captures a new graph (the two
 # most recent are kept).  Not captured (eager steps instead): CowMix drawn from the CPU generator (parity mode),
 # ClassMix / CutMix draws from the host generator or fixed (mixmasks.DRAW_SOURCE, set_draws), a
@@ -419,8 +465,12 @@ def _graph_key(model, ema_model, optimizer, image, mask, unsup_a, unsup_b, epoch
         return None
     lrs = tuple(float(g['lr']) for o in opts for g in o.param_groups)
     shapes = tuple((tuple(t.shape), t.dtype) if t is not None else None for t in (image, mask, unsup_a, unsup_b))
+    sat = _adaptive_threshold(tc) if tc['use_semi_supervised'] else None
+    if sat is not None and sat.state is None:
+        return None   # the first update allocates the device state: an eager step
+    thr_key = _threshold_key(tc) if tc['use_semi_supervised'] else ('fixed', None, None)
     return step_key + (id(optimizer), opt_step, float(epoch > 25), lrs, shapes, id(config),
-                       _consistency_activation(tc), kind) + _consistency_loss_kind(tc)
+                       _consistency_activation(tc), kind) + _consistency_loss_kind(tc) + thr_key
 
 
 def _graph_step(key, model, ema_model, optimizer, image, mask, unsup_a, unsup_b, epoch, step, config):
@@ -529,6 +579,10 @@ def train(model, ema_model, optimizer, dataloader, unsupervised_dataloader, epoc
                 if summary_writer is not None:
                     summary_writer.add_scalar('train_classification_loss', float(red_cls), global_step)
                     summary_writer.add_scalar('train_unsupervised_loss', float(red_uns), global_step)
+                    sat = tc.get('confidence_threshold_state')
+                    if sat is not None and sat.tau() is not None:
+                        # rank 0's own tau (the states are per rank); read here, where the losses above already sync
+                        summary_writer.add_scalar('train_confidence_threshold', sat.tau(), global_step)
     _reduce_meters(meters, ('cls', 'sup', 'unsup', 'cm'), world)
     if rank == 0 and summary_writer is not None and meters['sup'].initialized:
         summary_writer.add_scalar('batch_time', meters['time'].average(), global_step)

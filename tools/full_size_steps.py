@@ -31,13 +31,14 @@ import torch.distributed as dist  # noqa: E402
 # semi-supervised step GFLOP per labelled image (3F sup fwd+bwd + 2F teacher + 3F consistency fwd+bwd)
 # (c2geo: the same convs; c6: C2's convs with a 19-class head, +0.1 %)
 STEP_GFLOP_PER_IMAGE = {'c2': 765.1, 'c2geo': 765.1, 'c2cutmix': 765.1, 'c3': 3855.8, 'c4': 3904.2, 'c5': 85.2, 'c6': 765.1,
-                        'c6classmix': 765.1, 'c6classmixce': 765.1, 'c6cutmixce': 765.1}
+                        'c6classmix': 765.1, 'c6classmixce': 765.1, 'c6cutmixce': 765.1, 'c6cutmixceadaptive': 765.1}
 PEAK = {'bfloat16': 2.5e15, 'float16': 2.5e15, 'float32': 0.16e15}   # dense MFMA (MI355X_MICROARCH.md)
 CFGS = {'c2': 'configs/c2_unet_r50.py', 'c2geo': 'configs/c2_unet_r50_geo.py', 'c3': 'configs/c3_deeplabv3_r101.py',
         'c4': 'configs/c4_msa_hrnet.py', 'c5': 'configs/c5_hardnet_disc.py',
         'c6': 'configs/c6_unet_r50_multiclass.py', 'c6classmix': 'configs/c6_unet_r50_classmix.py',
         'c2cutmix': 'configs/c2_unet_r50_cutmix.py', 'c6classmixce': 'configs/c6_unet_r50_classmix_ce.py',
-        'c6cutmixce': 'configs/c6_unet_r50_cutmix_ce.py'}
+        'c6cutmixce': 'configs/c6_unet_r50_cutmix_ce.py',
+        'c6cutmixceadaptive': 'configs/c6_unet_r50_cutmix_ce_adaptive.py'}
 MIX_MASK = {'kind': None}   # --mix-mask: the mixing mask of every config of the run (train['mix_mask'])
 
 
@@ -178,8 +179,21 @@ def graph_steps(name, path, dev, threshold, calibrate, eager_losses, n_eager=3, 
         g(*data)
     torch.cuda.synchronize()
     ms = 1e3 * (time.time() - t0) / n_replay
+    thr = threshold_record(tc)   # after n_eager + 2 + n_replay updates
+    if thr is not None:
+        thr['cm_mean_last_replay'] = float(g(*data)[2])
     del g, model, ema, opt
-    return ms, same, out, same_eager
+    return ms, same, out, same_eager, thr
+
+
+def threshold_record(tc):
+    """the adaptive thresholds' state (train['confidence_threshold_mode'] = 'adaptive'), None under 'fixed'"""
+    sat = tc.get('confidence_threshold_state')
+    if sat is None or sat.state is None:
+        return None
+    sd = sat.state_dict()
+    return {'momentum': sat.momentum, 'updates': sd['steps'], 'tau': sd['tau'],
+            'thr_c': [round(v, 6) for v in sat.thr.tolist()]}
 
 
 def run(name, path, dev, threshold=0.5, calibrate=True, layers=False, graph=False, loop=False):
@@ -225,12 +239,16 @@ def run(name, path, dev, threshold=0.5, calibrate=True, layers=False, graph=Fals
     rec['frac_of_dense_peak'] = round(tf * 1e12 / PEAK[rec['dtype']], 4)
     if conv:   # the conv engine of the extra probed step: MFMA and bytes rooflines (algorithmic flops / bytes)
         rec['conv_engine'] = conv
+    if threshold_record(tc) is not None:
+        rec['adaptive_threshold'] = threshold_record(tc)
     if 'adversarial' in tc:
         rec['loss_d'] = float(tc['adversarial']['last_loss_d'])
     if graph:   # the same steps replayed from a captured HIP graph (fresh build, same seeds)
         del model, ema, opt
         torch.cuda.empty_cache()
-        gms, same, gl, same_eager = graph_steps(name, path, dev, threshold, calibrate, out)
+        gms, same, gl, same_eager, gthr = graph_steps(name, path, dev, threshold, calibrate, out)
+        if gthr is not None:
+            rec['graph_adaptive_threshold'] = gthr
         rec['graph'] = {'ms_per_step': round(gms, 1), 'losses_bitwise_equal_eager': same, 'losses_steps_3_4': gl,
                         'rebuild_eager_steps_bitwise_equal': same_eager,
                         'frac_of_dense_peak': round(STEP_GFLOP_PER_IMAGE[name] * b / (gms / 1e3) / 1e3 * 1e12 /
