@@ -401,7 +401,8 @@ int ssseg_rmi_bwd(const float* logits, int64_t N, int64_t C, int64_t H, int64_t 
 enum { SSSEG_RED_NONE = 0, SSSEG_RED_MEAN = 1, SSSEG_RED_SUM = 2 };
 enum { SSSEG_LOSS_REDUCE = 0,      /* CE, Focal, the entropies, BCE 'sum': one scalar reduction */
        SSSEG_LOSS_OHEM = 1, SSSEG_LOSS_NFL = 2, SSSEG_LOSS_DICE_LOGITS = 3,
-       SSSEG_LOSS_DICE_PROB = 4    /* (B, 1, n) */ };
+       SSSEG_LOSS_DICE_PROB = 4,   /* (B, 1, n) */
+       SSSEG_LOSS_CE_LABELS = 5, SSSEG_LOSS_OHEM_LABELS = 6 };
 /* Workspace bytes of the loss `kind` at [B,C,HW]; 0 for an unknown kind or an empty shape. */
 size_t ssseg_segloss_workspace_bytes(int kind, int64_t B, int64_t C, int64_t HW);
 
@@ -423,6 +424,38 @@ int ssseg_ohem_fwd(const float* x, const float* t, int64_t B, int64_t C, int64_t
                    float* out, void* ws, size_t ws_bytes, ssseg_stream_t stream);
 int ssseg_ohem_bwd(const float* x, const float* t, int64_t B, int64_t C, int64_t HW, const float* gout, float* gx,
                    const void* ws, size_t ws_bytes, ssseg_stream_t stream);
+
+/* Cross-entropy on a label map with a void label: F.cross_entropy(x, y, weight, ignore_index, reduction,
+ * label_smoothing), the call inside the reference's lovasz.xloss (lovasz.py:227).  x [B,C,HW] f32, 2 <= C <= 64.
+ * labels [B,HW] read in place: int64 (SSSEG_LOVASZ_LABEL_I64) or uint8 (SSSEG_LOVASZ_LABEL_U8).  ignore_index: any
+ * integer, also one inside [0, C).  The labelled channel is selected by comparison, never by indexing with the label:
+ * a label outside [0, C) that is not ignore_index is void like it (it cannot be reported without a host sync and
+ * cannot read out of bounds).  weight: device f32 [C] or NULL (= 1).  0 <= label_smoothing < 1.
+ * Per valid pixel l = (1 - eps) w_y (-logp_y) + eps / C * sum_c w_c (-logp_c); a void pixel gives 0.
+ * SSSEG_RED_NONE: out [B,HW] (no workspace).  SSSEG_RED_SUM: out[0] = sum l.  SSSEG_RED_MEAN: out[0] = sum l /
+ * sum w_y over the valid pixels; everything void: 0/0 = NaN like torch, or 0 with empty_zero != 0.  The forward
+ * leaves the denominator in double 0 of ws, where the backward of SSSEG_RED_MEAN reads it (nothing is read on the
+ * host).  gx = g * d l / d x with g = gout[0] / denominator (mean), gout[0] (sum) or gout[b,pix] (none); void pixels
+ * get exact zeros (also when everything is void).  With weight == NULL and label_smoothing == 0 the per-pixel value
+ * and the gradient are bit for bit those of ssseg_ce_fwd/bwd on the one-hot target. */
+int ssseg_ce_labels_fwd(const float* x, const void* labels, int label_kind, int64_t B, int64_t C, int64_t HW,
+                        const float* weight, int64_t ignore_index, float label_smoothing, int reduction,
+                        int empty_zero, float* out, void* ws, size_t ws_bytes, ssseg_stream_t stream);
+int ssseg_ce_labels_bwd(const float* x, const void* labels, int label_kind, int64_t B, int64_t C, int64_t HW,
+                        const float* weight, int64_t ignore_index, float label_smoothing, int reduction,
+                        const float* gout, float* gx, const void* ws, size_t ws_bytes, ssseg_stream_t stream);
+
+/* OhemCrossEntropy (losses.py:51-69) on a label map, with the void handling of the HRNet original: pred = softmax(x)
+ * at the label; order statistic, threshold and mean over the valid pixels only: k = min(min_kept, n_valid - 1),
+ * threshold = max(sorted(pred)[k], thresh), out[0] = mean CE over the valid pixels with pred < threshold.  Void
+ * pixels (ignore_label, or any label outside [0, C)) carry pred = +inf: their keys sort last and are never kept.
+ * n_valid is counted on the device (exact per-block counts) and clamps k before the first radix pass.  n_valid == 0:
+ * NaN loss, zero gradient.  ws as for ssseg_ohem_fwd, plus n_valid in double 2.  Labels as for ssseg_ce_labels_fwd. */
+int ssseg_ohem_labels_fwd(const float* x, const void* labels, int label_kind, int64_t B, int64_t C, int64_t HW,
+                          int64_t ignore_label, float thresh, int64_t min_kept, float* out, void* ws, size_t ws_bytes,
+                          ssseg_stream_t stream);
+int ssseg_ohem_labels_bwd(const float* x, const void* labels, int label_kind, int64_t B, int64_t C, int64_t HW,
+                          const float* gout, float* gx, const void* ws, size_t ws_bytes, ssseg_stream_t stream);
 
 /* FocalLoss (losses.py:72-90), n elements: out[0] = mean((1 - p_t)^gamma * (t alpha + (1-t)(1-alpha)) * bce(x, t)),
  * p_t = t p + (1-t)(1-p), p = sigmoid(x).  Backward: autograd of that expression (valid for soft targets). */

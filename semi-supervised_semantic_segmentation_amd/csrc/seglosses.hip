@@ -258,6 +258,223 @@ __global__ void ohem_bwd_kernel(const float* x, const float* t, int C, int64_t H
   }
 }
 
+// ---- label-map CE and OHEM: labels [B,HW] uint8 / int64 read in place, with a void label ----
+// The labelled channel is selected by comparison over the registers, never by indexing memory with the label: a label
+// outside [0, C) that is not the ignore value selects nothing and is void like it (no host check without a sync).
+__device__ __forceinline__ int64_t load_label(const void* labels, int kind, int64_t q) {
+  return kind == SSSEG_LOVASZ_LABEL_U8 ? (int64_t)((const unsigned char*)labels)[q] : ((const int64_t*)labels)[q];
+}
+__device__ __forceinline__ bool label_valid(int64_t lab, int64_t ignore, int C) {
+  return lab != ignore && lab >= 0 && lab < (int64_t)C;
+}
+
+// p_c - [c == y] with p_c = e_c * inv rounded before the subtraction: what the dense kernels'
+// (e_c * inv) * sum(t) - t_c gives on a one-hot target, whether or not the compiler fuses that (the product by
+// sum(t) = 1 is exact).  Here the fusion of e_c * inv into the subtraction would round once instead of twice, so
+// contraction is off.
+__device__ __forceinline__ float prob_minus_onehot(float e, float inv, float t) {
+#pragma clang fp contract(off)
+  const float p = e * inv;
+  return p - t;
+}
+
+// F.cross_entropy(x, y, weight, ignore_index, reduction, label_smoothing) per pixel:
+// l = (1 - eps) w_y (-logp_y) + eps / C sum_c w_c (-logp_c), 0 where void.  part: (sum l, sum w_y) per block.
+// No weight and eps == 0: -(d_y - lse), the dense kernel's value on a one-hot target, bit for bit.
+template <int CM>
+__global__ void __launch_bounds__(RED_THREADS) cel_fwd_kernel(const float* x, const void* labels, int kind, int C,
+                                                              int64_t HW, int64_t npix, const float* weight,
+                                                              int64_t ignore, float eps, float* per_px, double* part) {
+  __shared__ double red[RED_THREADS / 64];
+  const bool plain = !weight && eps == 0.f;
+  const float a = 1.f - eps, bs = eps / (float)C;
+  double num = 0.0, den = 0.0;
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < npix; q += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t lab = load_label(labels, kind, q);
+    float l = 0.f, wy = 0.f;
+    if (label_valid(lab, ignore, C)) {
+      const int y = (int)lab;
+      const int64_t b = q / HW, off = b * C * HW + (q - b * HW);
+      Soft<CM> sm;
+      sm.load(x + off, C, HW);
+      const float lse = logf(sm.s);
+      float dy = 0.f;
+#pragma unroll
+      for (int c = 0; c < CM; ++c)
+        if (c == y) dy = sm.d[c];
+      if (plain) {
+        l = -(dy - lse);
+        wy = 1.f;
+      } else {
+        float all = 0.f;
+        wy = 1.f;
+#pragma unroll
+        for (int c = 0; c < CM; ++c) {
+          if (c < C) {
+            const float wc = weight ? weight[c] : 1.f;
+            if (c == y) wy = wc;
+            all += wc * (lse - sm.d[c]);
+          }
+        }
+        l = a * wy * (lse - dy) + bs * all;
+      }
+    }
+    if (per_px) per_px[q] = l;
+    num += (double)l;
+    den += (double)wy;
+  }
+  if (part) {
+    num = block_sum(num, red);
+    den = block_sum(den, red);
+    if (threadIdx.x == 0) {
+      part[2 * blockIdx.x] = num;
+      part[2 * blockIdx.x + 1] = den;
+    }
+  }
+}
+
+// hdr[0] = sum of w_y over the valid pixels (the 'mean' denominator, read by the backward); out[0] = num / den
+// ('mean'; 0/0 = NaN like torch when everything is void, 0 with empty_zero) or num ('sum')
+__global__ void __launch_bounds__(RED_THREADS) cel_final_kernel(const double* part, int nparts, int mean,
+                                                                int empty_zero, double* hdr, float* out) {
+  __shared__ double red[RED_THREADS / 64];
+  double num = 0.0, den = 0.0;
+  for (int i = threadIdx.x; i < nparts; i += blockDim.x) {
+    num += part[2 * i];
+    den += part[2 * i + 1];
+  }
+  num = block_sum(num, red);
+  den = block_sum(den, red);
+  if (threadIdx.x == 0) {
+    hdr[0] = den;
+    if (!mean) out[0] = (float)num;
+    else out[0] = (den == 0.0 && empty_zero) ? 0.f : (float)(num / den);
+  }
+}
+
+// gx_c = g * ((a w_y + bs sum_k w_k) p_c - a w_y [c == y] - bs w_c), zeros where void; g = gout[0] / hdr[0] (mean),
+// gout[0] (sum) or gout[q] (none).  No weight and eps == 0: g * (p_c - [c == y]) as the dense kernel rounds it.
+template <int CM>
+__global__ void cel_bwd_kernel(const float* x, const void* labels, int kind, int C, int64_t HW, int64_t npix,
+                               const float* weight, int64_t ignore, float eps, int reduction, const double* hdr,
+                               const float* gout, float* gx) {
+  const bool plain = !weight && eps == 0.f;
+  const float a = 1.f - eps, bs = eps / (float)C;
+  float gs = 0.f;
+  if (reduction == SSSEG_RED_MEAN) gs = gout[0] / (float)hdr[0];
+  else if (reduction == SSSEG_RED_SUM) gs = gout[0];
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < npix; q += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = q / HW, off = b * C * HW + (q - b * HW);
+    const int64_t lab = load_label(labels, kind, q);
+    if (!label_valid(lab, ignore, C)) {
+      for (int c = 0; c < C; ++c) gx[off + c * HW] = 0.f;
+      continue;
+    }
+    const int y = (int)lab;
+    Soft<CM> sm;
+    sm.load(x + off, C, HW);
+    const float g = reduction == SSSEG_RED_NONE ? gout[q] : gs;
+    const float inv = 1.f / sm.s;
+    if (plain) {
+#pragma unroll
+      for (int c = 0; c < CM; ++c)
+        if (c < C) gx[off + c * HW] = g * prob_minus_onehot(sm.e[c], inv, c == y ? 1.f : 0.f);
+    } else {
+      float wy = 1.f, sw = 0.f;
+#pragma unroll
+      for (int c = 0; c < CM; ++c) {
+        if (c < C) {
+          const float wc = weight ? weight[c] : 1.f;
+          if (c == y) wy = wc;
+          sw += wc;
+        }
+      }
+      const float ay = a * wy, tot = ay + bs * sw;
+#pragma unroll
+      for (int c = 0; c < CM; ++c) {
+        if (c < C) {
+          const float wc = weight ? weight[c] : 1.f;
+          gx[off + c * HW] = g * (sm.e[c] * inv * tot - (c == y ? ay : 0.f) - bs * wc);
+        }
+      }
+    }
+  }
+}
+
+// OHEM on a label map: pred = softmax at the label, +inf where void (its key sorts after every valid key and
+// pred < threshold never holds), ce = 0 there; cnt[block] = the block's exact number of valid pixels
+template <int CM>
+__global__ void __launch_bounds__(RED_THREADS) ohl_px_kernel(const float* x, const void* labels, int kind, int C,
+                                                             int64_t HW, int64_t npix, int64_t ignore, float* pred,
+                                                             float* ce, double* cnt) {
+  __shared__ double red[RED_THREADS / 64];
+  double nv = 0.0;
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < npix; q += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t lab = load_label(labels, kind, q);
+    if (!label_valid(lab, ignore, C)) {
+      pred[q] = INFINITY;
+      ce[q] = 0.f;
+      continue;
+    }
+    const int y = (int)lab;
+    const int64_t b = q / HW, off = b * C * HW + (q - b * HW);
+    Soft<CM> sm;
+    sm.load(x + off, C, HW);
+    const float lse = logf(sm.s);
+    float dy = 0.f, ey = 0.f;
+#pragma unroll
+    for (int c = 0; c < CM; ++c) {
+      if (c == y) {
+        dy = sm.d[c];
+        ey = sm.e[c];
+      }
+    }
+    pred[q] = ey / sm.s;
+    ce[q] = -(dy - lse);
+    nv += 1.0;
+  }
+  nv = block_sum(nv, red);
+  if (threadIdx.x == 0) cnt[blockIdx.x] = nv;
+}
+
+// n_valid (integer-valued fp64 sum: exact in any order) -> hdr[2]; rank k = min(min_kept, n_valid - 1) for the
+// radix select (0 when nothing is valid: the statistic is then a void key, +inf, and nothing is kept)
+__global__ void __launch_bounds__(RED_THREADS) ohl_init_kernel(const double* cnt, int nparts, unsigned min_kept,
+                                                               double* hdr, unsigned* sel, unsigned* hist) {
+  __shared__ double red[RED_THREADS / 64];
+  for (int i = threadIdx.x; i < 4 * 256; i += blockDim.x) hist[i] = 0u;
+  double nv = 0.0;
+  for (int i = threadIdx.x; i < nparts; i += blockDim.x) nv += cnt[i];
+  nv = block_sum(nv, red);
+  if (threadIdx.x == 0) {
+    const unsigned n = (unsigned)nv;
+    hdr[2] = nv;
+    sel[0] = 0u;
+    sel[1] = n == 0u ? 0u : (min_kept < n - 1u ? min_kept : n - 1u);
+  }
+}
+
+template <int CM>
+__global__ void ohl_bwd_kernel(const float* x, const void* labels, int kind, int C, int64_t HW, int64_t npix,
+                               const double* hdr, const float* pred, const float* gout, float* gx) {
+  const float thr = (float)hdr[0];
+  const float gs = gout[0] / (float)hdr[1];
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < npix; q += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = q / HW, off = b * C * HW + (q - b * HW);
+    if (!(pred[q] < thr)) {   // void pixels hold +inf
+      for (int c = 0; c < C; ++c) gx[off + c * HW] = 0.f;
+      continue;
+    }
+    const int y = (int)load_label(labels, kind, q);
+    Soft<CM> sm;
+    sm.load(x + off, C, HW);
+    const float inv = 1.f / sm.s;
+#pragma unroll
+    for (int c = 0; c < CM; ++c)
+      if (c < C) gx[off + c * HW] = gs * prob_minus_onehot(sm.e[c], inv, c == y ? 1.f : 0.f);
+  }
+}
+
 // ---- FocalLoss ----
 __global__ void __launch_bounds__(RED_THREADS) focal_partial_kernel(const float* x, const float* t, int64_t n,
                                                                     float alpha, float alpha1, float gamma,
@@ -733,6 +950,8 @@ extern "C" size_t ssseg_segloss_workspace_bytes(int kind, int64_t B, int64_t C, 
     case SSSEG_LOSS_NFL: return hdr + d * (BC * PLANE_CHUNKS * 3 + BC * 3 + BC * PLANE_CHUNKS) + f * (BC + B);
     case SSSEG_LOSS_DICE_LOGITS: return hdr + d * BC * PLANE_CHUNKS * 3 + f * (4 * BC + B);
     case SSSEG_LOSS_DICE_PROB: return hdr + d * (size_t)B * PLANE_CHUNKS * 2 + f * 2 * (size_t)B;
+    case SSSEG_LOSS_CE_LABELS: return hdr + d * 2 * RED_BLOCKS;
+    case SSSEG_LOSS_OHEM_LABELS: return hdr + d * 2 * RED_BLOCKS + 4 * (4 + 4 * 256) + f * 2 * (size_t)(B * HW);
   }
   return 0;
 }
@@ -805,6 +1024,93 @@ extern "C" int ssseg_ohem_bwd(const float* x, const float* t, int64_t B, int64_t
   const OhemWs w = ohem_ws(const_cast<void*>(ws), npix);
   SEG_LAUNCH_C(ohem_bwd_kernel, C, dim3(ssseg_grid(npix, 256)), dim3(256), (hipStream_t)stream, x, t, (int)C, HW,
                npix, (const double*)w.hdr, (const float*)w.pred, gout, gx);
+  SSSEG_LAUNCH_CHECK();
+  return 0;
+}
+
+static bool bad_labels(const void* labels, int label_kind, int64_t C) {
+  return !labels || C < 2 || (label_kind != SSSEG_LOVASZ_LABEL_I64 && label_kind != SSSEG_LOVASZ_LABEL_U8);
+}
+
+extern "C" int ssseg_ce_labels_fwd(const float* x, const void* labels, int label_kind, int64_t B, int64_t C,
+                                   int64_t HW, const float* weight, int64_t ignore_index, float label_smoothing,
+                                   int reduction, int empty_zero, float* out, void* ws, size_t ws_bytes,
+                                   ssseg_stream_t stream) {
+  if (!x || !out || bad_shape(B, C, HW) || bad_labels(labels, label_kind, C)) return SSSEG_EINVAL;
+  if (reduction < SSSEG_RED_NONE || reduction > SSSEG_RED_SUM) return SSSEG_EINVAL;
+  if (!(label_smoothing >= 0.f && label_smoothing < 1.f)) return SSSEG_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t npix = B * HW;
+  const int nb = red_blocks(npix);
+  if (reduction == SSSEG_RED_NONE) {
+    SEG_LAUNCH_C(cel_fwd_kernel, C, dim3(nb), dim3(RED_THREADS), s, x, labels, label_kind, (int)C, HW, npix, weight,
+                 ignore_index, label_smoothing, out, (double*)nullptr);
+  } else {
+    SEG_WS_CHECK(SSSEG_LOSS_CE_LABELS, B, C, HW);
+    double* hdr = (double*)ws;
+    double* part = hdr + HDR;
+    SEG_LAUNCH_C(cel_fwd_kernel, C, dim3(nb), dim3(RED_THREADS), s, x, labels, label_kind, (int)C, HW, npix, weight,
+                 ignore_index, label_smoothing, (float*)nullptr, part);
+    hipLaunchKernelGGL(cel_final_kernel, dim3(1), dim3(RED_THREADS), 0, s, (const double*)part, nb,
+                       (int)(reduction == SSSEG_RED_MEAN), empty_zero, hdr, out);
+  }
+  SSSEG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ssseg_ce_labels_bwd(const float* x, const void* labels, int label_kind, int64_t B, int64_t C,
+                                   int64_t HW, const float* weight, int64_t ignore_index, float label_smoothing,
+                                   int reduction, const float* gout, float* gx, const void* ws, size_t ws_bytes,
+                                   ssseg_stream_t stream) {
+  if (!x || !gout || !gx || bad_shape(B, C, HW) || bad_labels(labels, label_kind, C)) return SSSEG_EINVAL;
+  if (reduction < SSSEG_RED_NONE || reduction > SSSEG_RED_SUM) return SSSEG_EINVAL;
+  if (!(label_smoothing >= 0.f && label_smoothing < 1.f)) return SSSEG_EINVAL;
+  if (reduction == SSSEG_RED_MEAN) SEG_WS_CHECK(SSSEG_LOSS_CE_LABELS, B, C, HW);   // the denominator lives there
+  const int64_t npix = B * HW;
+  SEG_LAUNCH_C(cel_bwd_kernel, C, dim3(ssseg_grid(npix, 256)), dim3(256), (hipStream_t)stream, x, labels, label_kind,
+               (int)C, HW, npix, weight, ignore_index, label_smoothing, reduction, (const double*)ws, gout, gx);
+  SSSEG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ssseg_ohem_labels_fwd(const float* x, const void* labels, int label_kind, int64_t B, int64_t C,
+                                     int64_t HW, int64_t ignore_label, float thresh, int64_t min_kept, float* out,
+                                     void* ws, size_t ws_bytes, ssseg_stream_t stream) {
+  if (!x || !out || bad_shape(B, C, HW) || bad_labels(labels, label_kind, C) || min_kept < 0) return SSSEG_EINVAL;
+  SEG_WS_CHECK(SSSEG_LOSS_OHEM_LABELS, B, C, HW);
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t npix = B * HW;
+  const OhemWs w = ohem_ws(ws, npix);
+  const unsigned k = (unsigned)(min_kept < npix ? min_kept : npix);   // clamped to n_valid - 1 on the device
+  const int nb = red_blocks(npix);
+  SEG_LAUNCH_C(ohl_px_kernel, C, dim3(nb), dim3(RED_THREADS), s, x, labels, label_kind, (int)C, HW, npix,
+               ignore_label, w.pred, w.ce, w.part);
+  hipLaunchKernelGGL(ohl_init_kernel, dim3(1), dim3(RED_THREADS), 0, s, (const double*)w.part, nb, k, w.hdr, w.sel,
+                     w.hist);
+  for (int pass = 0; pass < 4; ++pass) {
+    const int shift = 24 - 8 * pass;
+    hipLaunchKernelGGL(ohem_hist_kernel, dim3(nb), dim3(256), 0, s, (const float*)w.pred, npix,
+                       (const unsigned*)w.sel, w.hist + 256 * pass, shift);
+    hipLaunchKernelGGL(ohem_pick_kernel, dim3(1), dim3(256), 0, s, w.sel, (const unsigned*)(w.hist + 256 * pass),
+                       shift);
+  }
+  hipLaunchKernelGGL(ohem_sum_kernel, dim3(nb), dim3(RED_THREADS), 0, s, (const float*)w.pred, (const float*)w.ce,
+                     npix, (const unsigned*)w.sel, thresh, w.part);
+  hipLaunchKernelGGL(ohem_final_kernel, dim3(1), dim3(RED_THREADS), 0, s, (const double*)w.part, nb,
+                     (const unsigned*)w.sel, thresh, w.hdr, out);
+  SSSEG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ssseg_ohem_labels_bwd(const float* x, const void* labels, int label_kind, int64_t B, int64_t C,
+                                     int64_t HW, const float* gout, float* gx, const void* ws, size_t ws_bytes,
+                                     ssseg_stream_t stream) {
+  if (!x || !gout || !gx || bad_shape(B, C, HW) || bad_labels(labels, label_kind, C)) return SSSEG_EINVAL;
+  SEG_WS_CHECK(SSSEG_LOSS_OHEM_LABELS, B, C, HW);
+  const int64_t npix = B * HW;
+  const OhemWs w = ohem_ws(const_cast<void*>(ws), npix);
+  SEG_LAUNCH_C(ohl_bwd_kernel, C, dim3(ssseg_grid(npix, 256)), dim3(256), (hipStream_t)stream, x, labels, label_kind,
+               (int)C, HW, npix, (const double*)w.hdr, (const float*)w.pred, gout, gx);
   SSSEG_LAUNCH_CHECK();
   return 0;
 }

@@ -3,7 +3,10 @@
   CalculateLoss                           losses.py:8-22   (bilinear resize of each prediction + weighted sum)
   DenseCrossEntropyLossWithLogits         losses.py:25-39  (reduction 'mean' / 'none', soft targets)
   DenseBinaryCrossEntropyLossWithLogits   losses.py:41-48  (reduction 'mean' / 'sum' / 'none')
-  OhemCrossEntropy                        losses.py:51-69  (order statistic by a device radix select, no host sync)
+  OhemCrossEntropy                        losses.py:51-69  (order statistic by a device radix select, no host sync;
+                                          a [B, H, W] target is a label map with a void label)
+  CrossEntropyLossWithLogits              lovasz.py:227    (F.cross_entropy on a [B, H, W] label map: void label, class
+                                          weights, label smoothing; lovasz.xloss itself keeps raising)
   FocalLoss                               losses.py:72-90
   NormalizedFocalLossSigmoid              losses.py:93-151 (detach_delimeter=True, scalar weight; _k_sum on the device)
   DiceWithLogitsLoss                      losses.py:157-167
@@ -32,7 +35,7 @@ class CalculateLoss:
 
     def __call__(self, predictions_list, target):
         total = None
-        size = (target.size(2), target.size(3))
+        size = tuple(target.shape[-2:])   # [B, C, H, W] targets and [B, H, W] label maps alike
         for idx, prediction in enumerate(predictions_list):
             prediction = ops.interpolate_bilinear(prediction, size, align_corners=False)
             for spec in self.losses:
@@ -66,14 +69,43 @@ class DenseBinaryCrossEntropyLossWithLogits(nn.Module):
         return ops.bce_with_logits(input, target, self.reduction)
 
 
+class CrossEntropyLossWithLogits(nn.Module):
+    """nn.CrossEntropyLoss on a label map: logits [B, C, H, W] (2 <= C <= 64) against labels [B, H, W] (uint8 or
+    int64, read in place) with a void label, optional class weights and label smoothing: the F.cross_entropy call of
+    the reference's lovasz.xloss (lovasz.py:227), which lovasz.xloss itself still refuses here.  A label outside
+    [0, C) that is not ignore_index counts as void too (torch raises on it; the kernels cannot without a host sync).
+    empty: what 'mean' gives when every pixel is void, 'nan' like torch or 'zero'."""
+
+    def __init__(self, weight=None, ignore_index=255, reduction='mean', label_smoothing=0.0, empty='nan'):
+        super().__init__()
+        self.register_buffer('weight', None if weight is None else torch.as_tensor(weight, dtype=torch.float32))
+        self.ignore_index = ignore_index
+        self.reduction = reduction
+        self.label_smoothing = label_smoothing
+        self.empty = empty
+
+    def forward(self, input, target):
+        weight = self.weight
+        if weight is not None and weight.device != input.device:
+            weight = self.weight = weight.to(input.device)
+        return ops.cross_entropy_labels(input, target, weight, self.ignore_index, self.reduction,
+                                        self.label_smoothing, self.empty)
+
+
 class OhemCrossEntropy(nn.Module):
-    def __init__(self, thres=0.7, min_kept=100000):
+    """losses.py:51-69.  A target [B, H, W] is a label map (uint8 / int64) whose ignore_label pixels are void, as in
+    the HRNet original the reference's class was taken from; a [B, C, H, W] target takes the dense path."""
+
+    def __init__(self, thres=0.7, min_kept=100000, ignore_label=255):
         super().__init__()
         self.thresh = thres
         self.min_kept = max(1, min_kept)
+        self.ignore_label = ignore_label
         self.criterion = DenseCrossEntropyLossWithLogits(reduction='none')
 
     def forward(self, logits, target):
+        if target.dim() == logits.dim() - 1:
+            return ops.ohem_cross_entropy_labels(logits, target, self.thresh, self.min_kept, self.ignore_label)
         return ops.ohem_cross_entropy(logits, target, self.thresh, self.min_kept)
 
 

@@ -99,6 +99,10 @@ SIGS = {
     'ssseg_ce_bwd': (i32, [vp, vp, i64, i64, i64, i32, vp, vp, vp]),
     'ssseg_ohem_fwd': (i32, [vp, vp, i64, i64, i64, f32, i64, vp, vp, sz, vp]),
     'ssseg_ohem_bwd': (i32, [vp, vp, i64, i64, i64, vp, vp, vp, sz, vp]),
+    'ssseg_ce_labels_fwd': (i32, [vp, vp, i32, i64, i64, i64, vp, i64, f32, i32, i32, vp, vp, sz, vp]),
+    'ssseg_ce_labels_bwd': (i32, [vp, vp, i32, i64, i64, i64, vp, i64, f32, i32, vp, vp, vp, sz, vp]),
+    'ssseg_ohem_labels_fwd': (i32, [vp, vp, i32, i64, i64, i64, i64, f32, i64, vp, vp, sz, vp]),
+    'ssseg_ohem_labels_bwd': (i32, [vp, vp, i32, i64, i64, i64, vp, vp, vp, sz, vp]),
     'ssseg_focal_fwd': (i32, [vp, vp, i64, f64, f64, vp, vp, sz, vp]),
     'ssseg_focal_bwd': (i32, [vp, vp, i64, f64, f64, vp, vp, vp]),
     'ssseg_nfl_fwd': (i32, [vp, vp, i64, i64, i64, vp, vp, vp, vp, sz, vp]),
@@ -247,6 +251,7 @@ OPT_ADAM, OPT_ADAMOD, OPT_DIFFGRAD, OPT_DIFFMOD, OPT_RANGER = range(5)
 OPT_STATE_DOUBLES = 8
 RED_NONE, RED_MEAN, RED_SUM = 0, 1, 2
 LOSS_REDUCE, LOSS_OHEM, LOSS_NFL, LOSS_DICE_LOGITS, LOSS_DICE_PROB = 0, 1, 2, 3, 4
+LOSS_CE_LABELS, LOSS_OHEM_LABELS = 5, 6
 LOVASZ_PROBAS, LOVASZ_SOFTMAX, LOVASZ_HINGE = 0, 1, 2                        # SSSEG_LOVASZ_* (include/ssseg.h)
 LOVASZ_LABEL_I64, LOVASZ_LABEL_U8, LOVASZ_LABEL_F32, LOVASZ_LABEL_DENSE = 0, 1, 2, 3
 

@@ -935,6 +935,121 @@ def ohem_cross_entropy(x, t, thresh, min_kept, return_state=False):
     return out
 
 
+def _label_map(x, labels, name):
+    """(B, C, HW, labels as the kernels read them in place, label-kind code) of logits [B, C, ...] and a label map
+    with one label per pixel: uint8 stays, every other integer type becomes int64"""
+    if x.dim() < 3:
+        raise ValueError(f'{name}: expected logits [B, C, ...], got {tuple(x.shape)}')
+    B, C = x.shape[:2]
+    HW = x[0, 0].numel()
+    if not 2 <= C <= 64:
+        raise ValueError(f'{name}: {C} channels (the label-map kernels cover 2 <= C <= 64)')
+    if labels.dtype.is_floating_point or labels.dtype == torch.bool:
+        raise ValueError(f'{name}: the label map must be uint8 or int64, got {labels.dtype}')
+    if labels.dim() != x.dim() - 1 or labels.shape[0] != B or tuple(labels.shape[1:]) != tuple(x.shape[2:]):
+        raise ValueError(f'{name}: labels {tuple(labels.shape)} do not hold one label per pixel of {tuple(x.shape)}')
+    if labels.dtype == torch.uint8:
+        return B, C, HW, _c(labels), N.LOVASZ_LABEL_U8
+    return B, C, HW, _c(labels.long()), N.LOVASZ_LABEL_I64
+
+
+class _CELabels(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, labels, weight, args):
+        kind, B, C, HW, ignore, red, eps, empty_zero = args
+        if red == N.RED_NONE:
+            out = torch.empty((B,) + tuple(x.shape[2:]), device=x.device, dtype=torch.float32)
+        else:
+            out = torch.empty((), device=x.device, dtype=torch.float32)
+        # the workspace carries the 'mean' denominator to the backward: a tensor of its own
+        nb = N.lib().ssseg_segloss_workspace_bytes(N.LOSS_CE_LABELS, B, C, HW)
+        ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
+        N.call('ssseg_ce_labels_fwd', N.dev_ptr(x, 'input'), N.dev_ptr(labels, 'labels'), kind, B, C, HW,
+               N.dev_ptr(weight, 'weight'), ignore, eps, red, empty_zero, N.dev_ptr(out), N.dev_ptr(ws), nb,
+               N.stream())
+        ctx.save_for_backward(x, labels, weight, ws)
+        ctx.args = args
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, labels, weight, ws = ctx.saved_tensors
+        kind, B, C, HW, ignore, red, eps, _ = ctx.args
+        gx = torch.empty_like(x)
+        g = _c(g.float())
+        N.call('ssseg_ce_labels_bwd', N.dev_ptr(x), N.dev_ptr(labels), kind, B, C, HW, N.dev_ptr(weight), ignore, eps,
+               red, N.dev_ptr(g), N.dev_ptr(gx), N.dev_ptr(ws), ws.numel(), N.stream())
+        return gx, None, None, None
+
+
+def cross_entropy_labels(x, labels, weight=None, ignore_index=255, reduction='mean', label_smoothing=0.0,
+                         empty='nan'):
+    """F.cross_entropy(x, labels, weight, ignore_index=..., reduction=..., label_smoothing=...) on the device.
+    x [B, C, ...] f32 logits, 2 <= C <= 64; labels [B, ...] uint8 or int64, read in place.  ignore_index may lie
+    inside [0, C).  A label outside [0, C) that is not ignore_index is void as well: the kernels select the labelled
+    channel by comparison and nothing is checked on the host (that would be a sync).  'mean' divides by the sum of
+    w_y over the valid pixels; with everything void it is NaN like torch (empty='nan') or 0 (empty='zero'), and the
+    gradient is all zeros either way."""
+    name = 'cross_entropy_labels'
+    if reduction not in ('mean', 'sum', 'none'):
+        raise ValueError(f'{name}: {reduction} is not a valid value for reduction')
+    if empty not in ('nan', 'zero'):
+        raise ValueError(f"{name}: empty must be 'nan' or 'zero', got {empty!r}")
+    if not 0.0 <= float(label_smoothing) < 1.0:
+        raise ValueError(f'{name}: label_smoothing {label_smoothing} outside [0, 1)')
+    B, C, HW, labels, kind = _label_map(x, labels, name)
+    if weight is not None:
+        if weight.numel() != C:
+            raise ValueError(f'{name}: weight holds {weight.numel()} values for {C} classes')
+        weight = _c(weight.float()).reshape(C)
+    red = {'none': N.RED_NONE, 'mean': N.RED_MEAN, 'sum': N.RED_SUM}[reduction]
+    return _CELabels.apply(_c(x.float()), labels, weight,
+                           (kind, B, C, HW, int(ignore_index), red, float(label_smoothing), int(empty == 'zero')))
+
+
+class _OhemLabels(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, labels, args):
+        kind, B, C, HW, ignore, thresh, min_kept = args
+        out = torch.empty((), device=x.device, dtype=torch.float32)
+        # pred per pixel, the threshold and the kept count go to the backward in the workspace: a tensor of its own
+        nb = N.lib().ssseg_segloss_workspace_bytes(N.LOSS_OHEM_LABELS, B, C, HW)
+        ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
+        N.call('ssseg_ohem_labels_fwd', N.dev_ptr(x, 'logits'), N.dev_ptr(labels, 'labels'), kind, B, C, HW, ignore,
+               thresh, min_kept, N.dev_ptr(out), N.dev_ptr(ws), nb, N.stream())
+        ctx.save_for_backward(x, labels, ws)
+        ctx.meta = (kind, B, C, HW)
+        ctx.mark_non_differentiable(ws)
+        ctx.set_materialize_grads(False)
+        return out, ws
+
+    @staticmethod
+    def backward(ctx, g, g_ws):
+        x, labels, ws = ctx.saved_tensors
+        kind, B, C, HW = ctx.meta
+        gx = torch.empty_like(x)
+        g = _c(g.float())
+        N.call('ssseg_ohem_labels_bwd', N.dev_ptr(x), N.dev_ptr(labels), kind, B, C, HW, N.dev_ptr(g), N.dev_ptr(gx),
+               N.dev_ptr(ws), ws.numel(), N.stream())
+        return gx, None, None
+
+
+def ohem_cross_entropy_labels(x, labels, thresh, min_kept, ignore_label=255, return_state=False):
+    """OhemCrossEntropy on a label map [B, ...] (uint8 / int64) with a void label, as in the HRNet original: the
+    order statistic (k = min(min_kept, n_valid - 1)), the threshold and the mean run over the valid pixels only.
+    Labels outside [0, C) are void like ignore_label.  No valid pixel: NaN loss, zero gradient.  return_state: also
+    (threshold, kept count), a float64 [2] device view of the forward's workspace."""
+    name = 'ohem_cross_entropy_labels'
+    if int(min_kept) < 0:
+        raise ValueError(f'{name}: min_kept {min_kept} is negative')
+    B, C, HW, labels, kind = _label_map(x, labels, name)
+    out, ws = _OhemLabels.apply(_c(x.float()), labels,
+                                (kind, B, C, HW, int(ignore_label), float(thresh), int(min_kept)))
+    if return_state:
+        return out, ws[:16].view(torch.float64)
+    return out
+
+
 class _Focal(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, t, alpha, gamma):

@@ -305,6 +305,15 @@ def train_step(model, ema_model, optimizer, image, mask, unsup_a, unsup_b, epoch
         mixmasks.mix_mask_kind(tc)   # an unknown mask is refused before anything is launched
         _consistency_loss_kind(tc)   # and an unknown consistency loss, or 'ce' without the softmax
         _confidence_threshold_mode(tc)   # and an unknown threshold mode, or 'adaptive' without 'ce'
+    if mask.dim() == 3:
+        # a [B, H, W] label map (uint8 / int64, void pixels = tc['ignore_label']) goes to the losses as it is; the
+        # two branches below need a float [B, C, H, W] mask and refuse it before anything is launched
+        if adv is not None:
+            raise ValueError('train_step: the adversarial branch feeds the mask to the discriminator and needs a '
+                             f'[B, C, H, W] mask, got a label map {tuple(mask.shape)}')
+        if tc.get('device_augment') is not None:
+            raise NotImplementedError('train_step: device augmentation resamples a float [B, C, H, W] mask; a label '
+                                      f'map {tuple(mask.shape)} is not covered')
     features, pred_maps = model(image)
     classification_loss = tc['loss'](pred_maps, mask)
     sup_loss = classification_loss
@@ -601,7 +610,9 @@ _VALIDATE = {'miou': None, 'class_ious': None}
 def validate(model, dataloader, epoch, initial_step, summary_writer, config, device):
     """train.py:150-195: Dice on the nearest-resized argmax one-hot (the reference metric) plus mIoU over the
     whole validation set (lovasz.iou, lovasz.py:54-73) from the same device pass (ssseg_seg_metrics; a mask with other
-    than 2 channels takes ssseg_seg_metrics_mc with num_classes from the mask, and logs the per-class IoUs too)."""
+    than 2 channels takes ssseg_seg_metrics_mc with num_classes from the mask, and logs the per-class IoUs too).
+    A [B, H, W] label map (uint8 / int64) takes ssseg_seg_metrics_mc too, with the class count from the prediction's
+    channels and config['train'].get('ignore_label') as the void label, left out of every count."""
     model.eval()
     avg_loss, avg_metric = utils.AverageMeter(), utils.AverageMeter()
     rank = torch.distributed.get_rank() if torch.distributed.is_initialized() else 0
@@ -611,14 +622,18 @@ def validate(model, dataloader, epoch, initial_step, summary_writer, config, dev
         for sample in dataloader:
             image = sample['image'].to(device)
             mask = sample['semantic_mask'].to(device)
-            if seg is None:
+            features, pred_maps = model(image)
+            if seg is None and mask.dim() == 3:
+                # a label map: the C-class kernel, with the class count from the prediction and the void label left out
+                seg = ops.SegMetricsMC(device, pred_maps[-1].shape[1], config['train'].get('ignore_label'))
+            elif seg is None:
                 # two-channel masks: the reference's binary metric; any other class count: the C-class kernel, with
                 # the class count taken from the mask
                 seg = ops.SegMetrics(device) if mask.shape[1] == 2 else ops.SegMetricsMC(device, mask.shape[1])
-            features, pred_maps = model(image)
             loss = config['train']['loss'](pred_maps, mask)
             # argmax -> one-hot -> nearest resize -> dice (train.py:178-186) + lovasz.iou counts: one kernel
-            res = seg.update(pred_maps[-1], mask)
+            # (SegMetricsMC reads an int64 label map: a uint8 one is widened on the device)
+            res = seg.update(pred_maps[-1], mask.long() if mask.dim() == 3 else mask)
             metric = res[0:1].clone()[0]
             avg_loss.update(utils.reduce_tensor(loss.clone()) / world)
             avg_metric.update(utils.reduce_tensor(metric) / world)
