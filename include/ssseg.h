@@ -1100,6 +1100,45 @@ int ssseg_prob_onehot_mc(const float* logits, int64_t B, int64_t C, int64_t HW, 
                          float* onehot, ssseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Active-learning pool selection (csrc/active.hip; reference get_active_learning_partition.py:94-99, :118-134)
+ *
+ * Per-image uncertainty scores.  x: contiguous fp32 [B,C,HW] logits, 2 <= C <= 64, HW < 2^31, B <= 65535
+ * (SSSEG_EINVAL otherwise and for null pointers, checked on the host before any launch).  With p = softmax_c(x),
+ * p1 >= p2 the two largest probabilities of a pixel (a shared maximum gives p2 = p1) and every mean over the HW
+ * pixels of image b:  out[b,0] = mean(-sum_c p_c log p_c),  out[b,1] = mean(1 - p1),  out[b,2] = mean(1 - (p1 - p2)).
+ * The entropy is evaluated as log Z - sum_c p_c (x_c - m), m = max_c x_c, Z = sum_c exp(x_c - m): a saturated pixel
+ * scores 0 where the reference's p * log(p) gives 0 * -inf = NaN (a deliberate deviation).  Each logit is read once
+ * and nothing but out and ws is written.  Per-pixel terms fp32, sums fp64 per-block partials + one final block per
+ * image in ws (no floating-point atomics, bitwise reproducible); the blocks and the summation order of an image depend
+ * on (C, HW) only, so an image scores the same bits alone and inside any batch.  Graph-capturable. */
+size_t ssseg_uncertainty_workspace_bytes(int64_t B, int64_t C, int64_t HW);
+int ssseg_uncertainty_scores(const float* x, int64_t B, int64_t C, int64_t HW, float* out /* [B,3] */, void* ws,
+                             size_t ws_bytes, ssseg_stream_t stream);
+
+/* Deterministic k-means.  X: contiguous fp32 [N,D], 1 <= K <= 64, K <= N < 2^31, D < 2^31 (SSSEG_EINVAL otherwise, and
+ * for null pointers, tol < 0, max_iter outside [1, 100000]; workspace_bytes returns 0).  Every distance, sum and mean
+ * is fp64 on the fp32 data, summed in a fixed order without floating-point atomics: bitwise reproducible.
+ * A squared distance is summed by 64 lanes: lane l adds (x_d - c_d)^2 for d = l, l + 64, ... in that order, every
+ * difference, product and sum rounded on its own, then the lanes are added by the xor butterfly with offsets 32, 16,
+ * ..., 1.  A sum over the N points (inertia, the seeding scan) runs over 1024 contiguous slices of ceil(N / 1024)
+ * points, each in index order, the slice sums added in slice order.
+ * _seed: k-means++ from the uniforms u[K] (device, f32 in [0,1)).  seed_idx[0] = min(floor(u[0] N), N - 1); seed_idx[j]
+ * = the first i, in index order, whose inclusive cumulative sum of d2 exceeds u[j] * sum(d2), d2[i] the squared
+ * distance of point i to the nearest centre chosen so far (N - 1 where no cumulative sum exceeds it).  Writes
+ * seed_idx[K] (device int32) and centroids[K,D] (device fp64) = the chosen rows.
+ * _fit: Lloyd iterations from centroids[K,D] (fp64, in/out).  A point goes to the nearest centroid, the lowest index
+ * winning an exact tie; the new centroid is the mean of its points; a cluster that receives no point keeps its
+ * centroid.  Stops after max_iter iterations or once the squared centroid shift summed over the clusters is
+ * <= tol * mean_d Var(X[:,d]) (population variance): the decision is taken on the device, the iterations enqueued
+ * after it return at once, and nothing synchronises with the host.  On return (in stream order) labels[N] (int32) and
+ * inertia[0] (fp64) are those of the returned centroids and n_iter[0] (int32) counts the iterations that ran. */
+size_t ssseg_kmeans_workspace_bytes(int64_t N, int64_t D, int64_t K);
+int ssseg_kmeans_seed(const float* X, int64_t N, int64_t D, int64_t K, const float* u, int* seed_idx,
+                      double* centroids, void* ws, size_t ws_bytes, ssseg_stream_t stream);
+int ssseg_kmeans_fit(const float* X, int64_t N, int64_t D, int64_t K, double tol, int64_t max_iter, double* centroids,
+                     int* labels, double* inertia, int* n_iter, void* ws, size_t ws_bytes, ssseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Collectives: the data-parallel gradient all-reduce and the SyncBN sums
  * (reference distributed_trainer.py:34-38 -- SyncBatchNorm.convert_sync_batchnorm + DistributedDataParallel,
  * whose reducer all-reduces gradient buckets during backward; SyncBN all-reduces per-channel sums)

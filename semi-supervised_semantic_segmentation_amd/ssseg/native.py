@@ -118,6 +118,11 @@ SIGS = {
     'ssseg_bce_logits_red_fwd': (i32, [vp, vp, i64, i32, vp, vp, sz, vp]),
     'ssseg_bce_logits_red_bwd': (i32, [vp, vp, i64, i32, vp, vp, vp]),
     'ssseg_smooth_labels': (i32, [vp, vp, i64, f32, f32, vp]),
+    'ssseg_uncertainty_workspace_bytes': (sz, [i64, i64, i64]),
+    'ssseg_uncertainty_scores': (i32, [vp, i64, i64, i64, vp, vp, sz, vp]),
+    'ssseg_kmeans_workspace_bytes': (sz, [i64, i64, i64]),
+    'ssseg_kmeans_seed': (i32, [vp, i64, i64, i64, vp, vp, vp, vp, sz, vp]),
+    'ssseg_kmeans_fit': (i32, [vp, i64, i64, i64, f64, i64, vp, vp, vp, vp, vp, sz, vp]),
     'ssseg_prob_onehot': (i32, [vp, i64, i64, vp, vp, vp]),
     'ssseg_seg_metrics': (i32, [vp, I64P, i64, i64, vp, I64P, i64, i64, i64, vp, vp, vp, vp]),
     'ssseg_seg_metrics_mc': (i32, [vp, I64P, i64, i64, vp, I64P, i32, i32, i64, i64, i64, i64, i64, vp, vp, vp, vp,

@@ -1402,3 +1402,97 @@ def prob_onehot(logits, activation='sigmoid'):
         N.call('ssseg_prob_onehot_mc', N.dev_ptr(x, 'logits'), B, C, H * W, _ACTIVATIONS[activation], N.dev_ptr(prob),
                N.dev_ptr(onehot), N.stream())
     return prob, onehot
+
+
+# ------------------------------------------------------------------------------------------------
+# Active-learning pool selection (csrc/active.hip; reference get_active_learning_partition.py)
+# ------------------------------------------------------------------------------------------------
+def uncertainty_scores(logits):
+    """Per-image uncertainty of [B,C,...] logits -> float32 [B,3]: the means over the pixels of the softmax entropy
+    (get_active_learning_partition.py:94-95), of the least confidence 1 - p1 and of the margin score 1 - (p1 - p2).
+    The entropy is log Z - sum p (x - max x): 0, not NaN, on a saturated pixel.  One pass over the logits, bitwise
+    reproducible, and an image scores the same bits alone and inside a batch.  No autograd: this is selection.
+    Non-contiguous or non-fp32 logits are converted first."""
+    if logits.dim() < 3:
+        raise ValueError(f'uncertainty_scores: expected [B, C, ...] logits, got {tuple(logits.shape)}')
+    B, C = logits.shape[:2]
+    if not 2 <= C <= 64:
+        raise ValueError(f'uncertainty_scores: {C} channels (the kernel covers 2 <= C <= 64)')
+    if B < 1 or logits[0, 0].numel() < 1:
+        raise ValueError(f'uncertainty_scores: empty logits {tuple(logits.shape)}')
+    x = _c(logits.detach().float())
+    HW = x[0, 0].numel()
+    ptr = N.dev_ptr(x, 'logits')
+    out = torch.empty((B, 3), device=x.device, dtype=torch.float32)
+    nb = N.lib().ssseg_uncertainty_workspace_bytes(B, C, HW)
+    ws = N.workspace(nb, x.device)
+    N.call('ssseg_uncertainty_scores', ptr, B, C, HW, N.dev_ptr(out), N.dev_ptr(ws), nb, N.stream())
+    return out
+
+
+class KMeansResult(tuple):
+    """(centroids [K,D] float64, labels [N] int32, inertia 0-d float64, n_iter 0-d int32, seed_idx [K] int32 or None),
+    all on the device: reading one of them is the only synchronisation of a fit."""
+    __slots__ = ()
+    _fields = ('centroids', 'labels', 'inertia', 'n_iter', 'seed_idx')
+
+    def __new__(cls, *vals):
+        return tuple.__new__(cls, vals)
+
+    centroids = property(lambda s: s[0])
+    labels = property(lambda s: s[1])
+    inertia = property(lambda s: s[2])
+    n_iter = property(lambda s: s[3])
+    seed_idx = property(lambda s: s[4])
+
+
+def kmeans(X, k, *, u=None, init=None, tol=1e-6, max_iter=300):
+    """Deterministic k-means of the rows of X [N,D] (fp32 on the device), 1 <= k <= min(64, N), in fp64.
+
+    Exactly one of `u` (k uniforms in [0,1): k-means++ seeding, the scans in index order on the device) and `init`
+    ([k,D] initial centroids).  Lloyd iterations: lowest centroid index on an exact tie, fp64 means in a fixed order,
+    an empty cluster keeps its centroid; stops after max_iter iterations or once the summed squared centroid shift is
+    <= tol * mean_d Var(X[:,d]) (sklearn's rule), decided on the device.  -> KMeansResult."""
+    if (u is None) == (init is None):
+        raise ValueError('kmeans: give exactly one of u (k-means++ uniforms) and init (initial centroids)')
+    if not torch.is_tensor(X) or X.dim() != 2:
+        raise ValueError('kmeans: X must be a [N,D] tensor')
+    ptr = N.dev_ptr(X, 'X')
+    n, d = X.shape
+    k = int(k)
+    if not 1 <= k <= 64:
+        raise ValueError(f'kmeans: k = {k} (1 <= k <= 64 is supported)')
+    if k > n:
+        raise ValueError(f'kmeans: k = {k} clusters for {n} points')
+    if d < 1:
+        raise ValueError('kmeans: X has no columns')
+    if not tol >= 0 or not 1 <= int(max_iter) <= 100000:
+        raise ValueError(f'kmeans: tol = {tol!r}, max_iter = {max_iter!r}')
+    X = _c(X.detach().float())
+    ptr = N.dev_ptr(X, 'X')
+    dev = X.device
+    nb = N.lib().ssseg_kmeans_workspace_bytes(n, d, k)
+    ws = N.workspace(nb, dev)
+    labels = torch.empty(n, device=dev, dtype=torch.int32)
+    inertia = torch.empty((), device=dev, dtype=torch.float64)
+    n_iter = torch.empty((), device=dev, dtype=torch.int32)
+    seed_idx = None
+    if u is not None:
+        u = torch.as_tensor(u, dtype=torch.float32).reshape(-1)
+        if u.numel() != k:
+            raise ValueError(f'kmeans: u must hold k = {k} uniforms, got {u.numel()}')
+        if bool(((u < 0) | (u >= 1)).any()):
+            raise ValueError('kmeans: u must lie in [0, 1)')
+        u = _c(u.to(dev))
+        cent = torch.empty((k, d), device=dev, dtype=torch.float64)
+        seed_idx = torch.empty(k, device=dev, dtype=torch.int32)
+        N.call('ssseg_kmeans_seed', ptr, n, d, k, N.dev_ptr(u), N.dev_ptr(seed_idx), N.dev_ptr(cent), N.dev_ptr(ws), nb,
+               N.stream())
+    else:
+        init = torch.as_tensor(init)
+        if tuple(init.shape) != (k, d):
+            raise ValueError(f'kmeans: init must be [{k},{d}], got {tuple(init.shape)}')
+        cent = init.detach().to(device=dev, dtype=torch.float64).contiguous().clone()
+    N.call('ssseg_kmeans_fit', ptr, n, d, k, float(tol), int(max_iter), N.dev_ptr(cent), N.dev_ptr(labels),
+           N.dev_ptr(inertia), N.dev_ptr(n_iter), N.dev_ptr(ws), nb, N.stream())
+    return KMeansResult(cent, labels, inertia, n_iter, seed_idx)
