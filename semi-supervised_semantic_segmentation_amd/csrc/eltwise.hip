@@ -235,6 +235,8 @@ __global__ void sgd_kernel(float* __restrict__ p, float* __restrict__ g, float* 
     const float d = wd != 0.f ? fmaf(pi, wd, gi) : gi;
     float b;
     if (mom != 0.f) {
+      // (HIP's __fmul_rn / __fadd_rn are the plain operators and this file is built with the default
+      // -ffp-contract=fast: the pair below compiles to ONE fma, fma(buf, mom, d) -- tests/exact_step.py pins that)
       b = first ? d : __fadd_rn(__fmul_rn(buf[i], mom), d);
       buf[i] = b;
     } else {

@@ -223,6 +223,8 @@ def test_clip_sgd_matches_torch(hip_device):
     ref = torch.cat([q.detach().reshape(-1) for q in ref_p]).numpy()
     np.testing.assert_allclose(flat_p.cpu().numpy(), ref, rtol=1e-5, atol=1e-6)
     np.testing.assert_allclose(shadow.float().cpu().numpy(), ref, rtol=1e-2, atol=1e-2)
+    # the shadow IS the parameters rounded to nearest even (tests/test_step_exact.py pins the bits against numpy too)
+    assert torch.equal(shadow.cpu().view(torch.int16), flat_p.cpu().to(torch.bfloat16).view(torch.int16))
 
 
 def _lovasz_hip(x, t, dev, gscale=1.0):
