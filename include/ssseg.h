@@ -810,6 +810,35 @@ typedef struct ssseg_pack_desc {
 } ssseg_pack_desc;
 int ssseg_weight_pack_batch(const ssseg_pack_desc* descs, int64_t n, int dt, ssseg_stream_t stream);
 
+/* The tail of a training step in ONE launch: ssseg_sgd_step (flag SGD), ssseg_ema_update into `ema` (flag EMA), the
+ * bf16 ssseg_weight_pack_batch of every student pack (after SGD) and teacher pack (after EMA), and grad = 0 (flag
+ * CLEAR; without it grad is left clipped as ssseg_sgd_step leaves it).  Every output bit equals that sequence's.
+ * param, grad, momentum_buf and ema are flat fp32 arenas of one layout (16-byte aligned, a multiple of 4 elements
+ * long); descs (DEVICE memory, n_descs entries) must cover every arena element exactly once: a conv weight
+ * [A][B][Rs][Ss] at element offset off (off % 4 == 0, Rs * Ss <= 135) with its npacks packs packs[pack0 ..], or a
+ * range of n elements without packs (A == 0).  Ap / Bp: the largest row / column extent any of the weight's packs
+ * covers (layout 0: Kd / Cp, layout 1: Cp / Kd).  A pack has the ssseg_weight_pack arguments with Kr, Cd the weight's
+ * own extents; teacher != 0: packed from ema, else from param.  sqnorm (ssseg_sqnorm_accum of grad), max_norm,
+ * first_step and amp_state as in ssseg_sgd_step; a non-finite norm under amp_state skips the SGD part only.
+ * No allocation, synchronisation or host read: capture-safe. */
+#define SSSEG_PSTEP_SGD 1
+#define SSSEG_PSTEP_EMA 2
+#define SSSEG_PSTEP_CLEAR 4
+typedef struct ssseg_pstep_desc {
+  int64_t off, n;
+  int64_t A, B, Rs, Ss, Ap, Bp;
+  int64_t pack0, npacks;
+} ssseg_pstep_desc;
+typedef struct ssseg_pstep_pack {
+  void* dst;
+  int64_t teacher, layout;
+  int64_t Kd, Cp, r0, rstep, Rn, s0, sstep, Sn;
+} ssseg_pstep_pack;
+int ssseg_param_step(float* param, float* grad, float* momentum_buf, float* ema, const ssseg_pstep_desc* descs,
+                     int64_t n_descs, const ssseg_pstep_pack* packs, float lr, float momentum, float weight_decay,
+                     float max_norm, const float* sqnorm, int first_step, const float* amp_state, double alpha,
+                     int flags, ssseg_stream_t stream);
+
 /* Depthwise convolution (groups == channels; MobileNetV2 ConvBNReLU(groups=hidden), mobilenetv2.py:34-39,58).
  * The descriptor is the conv engine's with K == C and no output phases; weights packed [R*S][ldw] in the
  * compute dtype (ssseg_weight_pack layout 1, Kd = Kr = 1).  fwd takes the same fused epilogue as the conv

@@ -497,40 +497,50 @@ __global__ void __launch_bounds__(WM * WN * 64) wgrad_glds_kernel(const T16* __r
 
 // sum the split slabs and write dW in the requested layout: 0 = [K][R][S][C] (packed, C = physical),
 // 1 = [K][C_real][R][S] (PyTorch OIHW).  accumulate: dst += sum.
-// A block owns 64 consecutive outputs (256-byte slab rows, coalesced) and spreads the splits over its 16
-// waves: wave w sums splits w, w+16, ... in two chains (16 loads in flight per lane with the unroll), then
-// the 16 partials are added in wave order through LDS — a fixed order, so the result is deterministic.
+// A block owns 64 * V consecutive outputs and spreads the splits over its 16 waves: wave w sums splits w, w+16, ...
+// in two chains (16 loads in flight per lane with the unroll), then the 16 partials are added in wave order through
+// LDS — a fixed order, so the result is deterministic.  V = 4: a lane carries 4 consecutive outputs, each through the
+// very same sequence of additions, and loads them as one 16-byte piece (1 KB slab rows; the 4-byte rows of V = 1 ran
+// at 2.6 TB/s).  C % 4 == 0 (wg_geom_ok), so the 4 outputs share their filter row k and tap and total % 4 == 0: a
+// lane's piece is wholly inside or outside the slab.  V = 1 serves a slab that is not 16-byte aligned.
+template <int V>
 __global__ void __launch_bounds__(1024) wgrad_reduce_wide_kernel(const float* __restrict__ slab, int splits, int K, int R,
                                                             int S, int C, int c_real, int k_real,
                                                             float* __restrict__ dst, int layout, int accumulate) {
-  __shared__ float red[16][64];
+  typedef float vec_t __attribute__((ext_vector_type(V)));
+  __shared__ vec_t red[16][64];
   const long long KK = (long long)R * S * C;
   const long long total = (long long)K * KK;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const long long i = (long long)blockIdx.x * 64 + lane;
-  float a0 = 0.f, a1 = 0.f;
+  const long long i = ((long long)blockIdx.x * 64 + lane) * V;
+  vec_t a0 = 0.f, a1 = 0.f;
   if (i < total) {
     int z = w;
 #pragma unroll 8
     for (; z + 16 < splits; z += 32) {
-      a0 += slab[(long long)z * total + i];
-      a1 += slab[(long long)(z + 16) * total + i];
+      a0 += *(const vec_t*)(slab + (long long)z * total + i);
+      a1 += *(const vec_t*)(slab + (long long)(z + 16) * total + i);
     }
-    if (z < splits) a0 += slab[(long long)z * total + i];
+    if (z < splits) a0 += *(const vec_t*)(slab + (long long)z * total + i);
   }
   red[w][lane] = a0 + a1;
   __syncthreads();
   if (w != 0 || i >= total) return;
-  float sum = 0.f;
+  vec_t sum = 0.f;
 #pragma unroll
   for (int k = 0; k < 16; ++k) sum += red[k][lane];
   const int kk = (int)(i % KK), k = (int)(i / KK);
   const int c = kk % C, tap = kk / C, r = tap / S, s = tap % S;
-  if (c >= c_real || k >= k_real) return;
-  long long o;
-  if (layout == 0) o = ((long long)k * R * S + tap) * C + c;
-  else o = (((long long)k * c_real + c) * R + r) * S + s;
-  dst[o] = accumulate ? dst[o] + sum : sum;
+  if (k >= k_real) return;
+#pragma unroll
+  for (int e = 0; e < V; ++e) {
+    if (c + e >= c_real) break;
+    long long o;
+    if (layout == 0) o = ((long long)k * R * S + tap) * C + c + e;
+    else o = (((long long)k * c_real + c + e) * R + r) * S + s;
+    const float v = sum[e];
+    dst[o] = accumulate ? dst[o] + v : v;
+  }
 }
 
 // few splits: one thread per output, 4 independent chains
@@ -806,8 +816,14 @@ namespace {
 void launch_reduce(const float* slab, const ConvGeom& g, int splits, int64_t c_real, int64_t k_real, float* dw,
                    int layout, int accumulate, hipStream_t s) {
   const long long total = (long long)g.K * g.KK;
-  if (splits >= 64)   // many splits: spread them over the 16 waves of a block
-    hipLaunchKernelGGL(wgrad_reduce_wide_kernel, dim3((unsigned)((total + 63) / 64)), dim3(1024), 0, s, slab, splits,
+  // many splits: spread over a block's 16 waves.  Both widths give the same bits; the 16-byte one needs >= 128 blocks
+  // to pay (measured on zero slabs of 64 MB, us at V = 1 / 4: 4096 outputs 8.2 / 15.0, 16384: 13.8 / 17.0, 36864:
+  // 17.2 / 14.1, 147456: 21.9 / 15.3, 262144: 24.9 / 15.7)
+  if (splits >= 64 && total >= 32768 && g.C % 4 == 0 && ((uintptr_t)slab & 15) == 0)
+    hipLaunchKernelGGL(wgrad_reduce_wide_kernel<4>, dim3((unsigned)((total + 255) / 256)), dim3(1024), 0, s, slab,
+                       splits, g.K, g.R, g.S, g.C, (int)c_real, (int)k_real, dw, layout, accumulate);
+  else if (splits >= 64)
+    hipLaunchKernelGGL(wgrad_reduce_wide_kernel<1>, dim3((unsigned)((total + 63) / 64)), dim3(1024), 0, s, slab, splits,
                        g.K, g.R, g.S, g.C, (int)c_real, (int)k_real, dw, layout, accumulate);
   else
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(ssseg_grid(total, 256)), dim3(256), 0, s, slab, splits, g.K, g.R, g.S,

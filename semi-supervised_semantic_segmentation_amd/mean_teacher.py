@@ -11,12 +11,16 @@ from ssseg import nn as snn
 from ssseg import ops
 
 
-def update_ema_variables(model, ema_model, alpha):
+def update_ema_variables(model, ema_model, alpha, averaged=False):
+    """averaged=True: the fused parameter step (ssseg.param_step) has already averaged the parameters and repacked
+    the teacher's weights in this step; only the buffers are left."""
     with torch.no_grad():
         m = getattr(model, 'module', model)
         e = getattr(ema_model, 'module', ema_model)
         fa, ea = _arena.of(m), _arena.of(e)
-        if fa is not None and ea is not None and fa.compatible(ea):
+        if averaged:
+            pass
+        elif fa is not None and ea is not None and fa.compatible(ea):
             ops.ema_update_(ea.data, fa.data, alpha)
         else:
             for ep, p in zip(e.parameters(), m.parameters()):
@@ -25,7 +29,8 @@ def update_ema_variables(model, ema_model, alpha):
             eb, b = ed[ek], md[mk]
             if eb.data_ptr() != b.data_ptr() or eb.shape != b.shape:   # already aliased: data = data is a no-op
                 eb.data = b.data
-        snn.invalidate_packed(e)
+        if not averaged:
+            snn.invalidate_packed(e)
 
 
 def _buffer_slots(e, m):

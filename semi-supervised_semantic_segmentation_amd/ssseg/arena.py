@@ -33,6 +33,7 @@ class FlatArena:
                 if self.grad is not None and p.requires_grad:
                     p.grad = self.grad[o:o + n].view_as(p)
                 p._ssseg_arena = self
+        self.cleared = False     # set by the fused parameter step (ssseg.param_step), which wrote grad = 0 itself
         self._module_ref = module
         module._ssseg_arena = self
 
@@ -44,6 +45,9 @@ class FlatArena:
         return self.offsets[i], p.numel()
 
     def zero_grad(self):
+        if self.cleared:         # the fused parameter step has just cleared the arena: nothing was written since
+            self.cleared = False
+            return
         if self.grad is not None:
             if self.grad.is_cuda:
                 N.call('ssseg_zero', N.dev_ptr(self.grad), self.grad.numel() * 4, N.stream())

@@ -149,6 +149,7 @@ SIGS = {
     'ssseg_conv_igemm_epi_actmask': (i32, [vp, vp, vp, vp, i32, i32, vp, i32, f32, vp, sz, vp]),
     'ssseg_conv_igemm_epi_join': (i32, [vp, vp, vp, vp, i32, i32, vp, vp, i64, vp, sz, vp]),
     'ssseg_weight_pack_batch': (i32, [vp, i64, i32, vp]),
+    'ssseg_param_step': (i32, [vp, vp, vp, vp, vp, i64, vp, f32, f32, f32, f32, vp, i32, vp, f64, i32, vp]),
     'ssseg_dwconv_fwd': (i32, [vp, vp, vp, vp, i32, vp, vp]),
     'ssseg_dwconv_dgrad': (i32, [vp, vp, vp, vp, i32, vp]),
     'ssseg_dwconv_wgrad_workspace_bytes': (sz, [vp, i32]),

@@ -57,8 +57,15 @@ class SGD(torch.optim.Optimizer):
             self._first = False
 
     @torch.no_grad()
-    def step(self, closure=None, max_norm=0.0):
-        """max_norm > 0 clips the global gradient L2 norm first (clip_grad_norm_, train.py:122)."""
+    def step(self, closure=None, max_norm=0.0, fused=None):
+        """max_norm > 0 clips the global gradient L2 norm first (clip_grad_norm_, train.py:122).
+        fused = (plan, teacher arena, alpha) with plan = param_step.plan_for(student, teacher, self): this step, the
+        teacher's EMA, the repack of both models and the gradient clear as ONE launch (ssseg.param_step)."""
+        if fused is not None:
+            from . import param_step as _ps
+            plan, teacher_arena, alpha = fused
+            _ps.step(plan, self, teacher_arena, max_norm, alpha)
+            return None
         g = self.param_groups[0]
         sc = self.grad_scaler
         if (max_norm and max_norm > 0) or sc is not None:

@@ -23,6 +23,7 @@ import mixmasks
 import utils.utils as utils
 from ssseg import nn as snn
 from ssseg import ops
+from ssseg import param_step
 from ssseg.ddp import DistributedDataParallel as _DDP
 from ssseg.optim import SGD as _SGD, FusedOptimizer as _Fused
 
@@ -402,17 +403,24 @@ def train_step(model, ema_model, optimizer, image, mask, unsup_a, unsup_b, epoch
     snn.flush_wgrad()
     if ddp is not None:
         ddp.finish()
+    # clip + SGD, EMA, both repacks and the gradient clear as one launch where the models allow (ssseg.param_step)
+    plan = param_step.plan_for(_inner(model), _inner(ema_model), optimizer) if semi else None
     if step % tc['virtual_batch_size_multiplier'] == 0 and step != 0:
         clip = tc['gradient_clip_value']
-        if isinstance(optimizer, (_SGD, _Fused)):
+        if plan is not None:
+            optimizer.step(max_norm=clip, fused=(plan, _inner(ema_model)._ssseg_arena, tc['ema_model_alpha']))
+        elif isinstance(optimizer, (_SGD, _Fused)):
             optimizer.step(max_norm=clip)
         else:
             torch.nn.utils.clip_grad_norm_(_inner(model).parameters(), clip)
             optimizer.step()
         optimizer.zero_grad()
-        snn.invalidate_packed(_inner(model))
+        if plan is None:
+            snn.invalidate_packed(_inner(model))
+    elif plan is not None:   # no optimizer step (gradient accumulation, the reference's step 0): the EMA alone
+        param_step.step(plan, optimizer, _inner(ema_model)._ssseg_arena, 0.0, tc['ema_model_alpha'], sgd=False)
     if semi:
-        mean_teacher.update_ema_variables(model, ema_model, alpha=tc['ema_model_alpha'])
+        mean_teacher.update_ema_variables(model, ema_model, alpha=tc['ema_model_alpha'], averaged=plan is not None)
     return classification_loss.detach(), (unsup_loss.detach() if unsup_loss is not None else None), \
         (cm_mean.detach() if cm_mean is not None else None)
 

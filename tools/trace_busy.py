@@ -1,6 +1,6 @@
 """Device occupancy of the last N steps of a rocprofv3 kernel trace (csv) of bench.py: wall span per step, the union of
 the kernels' [start, end) intervals (busy), idle = span - busy, and the time with two or more kernels in flight (the
-side-stream overlap of train.train_step).  Steps are delimited by sgd_kernel launches.
+side-stream overlap of train.train_step).  Steps are delimited by sgd_kernel / param_step_kernel launches.
 
     python tools/trace_busy.py gpurun_out/r6_gtrace/g_kernel_trace.csv [--steps 7]
 """
@@ -17,7 +17,7 @@ def main():
     a = ap.parse_args()
     rows = sorted((int(r['Start_Timestamp']), int(r['End_Timestamp']), r['Kernel_Name'])
                   for r in csv.DictReader(open(a.trace)))
-    sgd = sorted(e for s, e, n in rows if 'sgd_kernel' in n)
+    sgd = sorted(e for s, e, n in rows if 'sgd_kernel' in n or 'param_step_kernel' in n)
     end = len(sgd) - 1 - a.skip_last
     t0, t1 = sgd[end - a.steps], sgd[end]
     sel = [(s, e) for s, e, _ in rows if s >= t0 and e <= t1]

@@ -1,4 +1,4 @@
-"""Per-family kernel time per step of the last N timed steps (delimited by sgd_kernel launches) from a rocprofv3
+"""Per-family kernel time per step of the last N timed steps (delimited by sgd_kernel / param_step_kernel launches) from a rocprofv3
 --output-format csv kernel trace of bench.py.
 
     python tools/trace_families.py gpurun_out/btrace/b_kernel_trace.csv [--steps 20]
@@ -27,7 +27,7 @@ def main():
     ap.add_argument('--steps', type=int, default=20)
     a = ap.parse_args()
     rows = [(r['Kernel_Name'], int(r['Start_Timestamp']), int(r['End_Timestamp'])) for r in csv.DictReader(open(a.trace))]
-    sgd = [s for n, s, e in rows if 'sgd_kernel' in n]
+    sgd = [s for n, s, e in rows if 'sgd_kernel' in n or 'param_step_kernel' in n]
     t0 = sgd[-(a.steps + 1)]
     sel = [(n, s, e) for n, s, e in rows if s > t0]
     span = (max(e for _, _, e in sel) - min(s for _, s, _ in sel)) / 1e6

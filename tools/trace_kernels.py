@@ -1,5 +1,5 @@
 """Per-kernel (function name, template arguments dropped) time per step over the last N timed steps (delimited by
-sgd_kernel launches) of a rocprofv3 --output-format csv kernel trace of bench.py.
+sgd_kernel launches, or the fused param_step_kernel's) of a rocprofv3 --output-format csv kernel trace of bench.py.
 
     python tools/trace_kernels.py gpurun_out/btrace/b_kernel_trace.csv [--steps 7]
 """
@@ -23,7 +23,7 @@ def main():
     ap.add_argument('--skip-last', type=int, default=0, help="steps at the end to leave out (the eager_n1 steps of bench.py --full)")
     a = ap.parse_args()
     rows = [(r['Kernel_Name'], int(r['Start_Timestamp']), int(r['End_Timestamp'])) for r in csv.DictReader(open(a.trace))]
-    sgd = sorted(s for n, s, e in rows if 'sgd_kernel' in n)
+    sgd = sorted(s for n, s, e in rows if 'sgd_kernel' in n or 'param_step_kernel' in n)
     end = len(sgd) - 1 - a.skip_last
     t0, t1 = sgd[end - a.steps], sgd[end]
     sel = [(n, s, e) for n, s, e in rows if t0 < s <= t1]
