@@ -1168,6 +1168,49 @@ int ssseg_kmeans_fit(const float* X, int64_t N, int64_t D, int64_t K, double tol
                      int* labels, double* inertia, int* n_iter, void* ws, size_t ws_bytes, ssseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Sliding-window evaluation (csrc/sliding.hip; build-defined: the reference evaluates the whole image in one forward).
+ * A window table is int32 [n][4], rows (b, y0, x0, flags): image index, origin of the window in the scale's working
+ * frame, flags bit 0 = horizontally mirrored, bit 1 = null window (padding of the last batch: contributes nothing).
+ * Bilinear sampling follows ssseg_bilinear_fwd with align_corners = 0.  No call allocates or synchronises.
+ * ------------------------------------------------------------------------------------------- */
+
+/* image [B,Cimg,Hs,Ws] of dtype dt (element strides image_strides4, host) -> crops [n,Cimg,ch,cw] of the same dtype
+ * (element strides crop_strides4, host: any layout, the model's own included).  Crop pixel (ly, lx) of window j is
+ * image (b, y0 + ly, x0 + lx'), lx' = cw - 1 - lx when the window is mirrored, else lx; coordinates outside
+ * [0,Hs) x [0,Ws) read as 0 (the zero padding of an image smaller than the crop); a null window, or one whose b is
+ * outside [0,B), is written as zeros.  windows: device table; 1 <= n <= 65535, 1 <= Cimg <= 64. */
+int ssseg_window_gather(const void* image, const int64_t* image_strides4, int64_t B, int64_t Cimg, int64_t Hs,
+                        int64_t Ws, const int32_t* windows, int64_t n, void* crops, const int64_t* crop_strides4,
+                        int64_t ch, int64_t cw, int dt, ssseg_stream_t stream);
+
+/* logits [n,C,h,w] f32 (element strides logit_strides4, host): the model's output for one batch of crops.  Window j's
+ * logits are upsampled bilinearly to ch x cw, un-mirrored if flagged, passed through `activation` over the C channels
+ * of the pixel (0: none, 1: sigmoid per channel, 2: softmax over C; expf, the formulas of ssseg_prob_onehot_mc),
+ * multiplied by the window weight and added into acc [B,C,Ha,Wa] f32 at (b, y0 + ly, x0 + lx); the weight alone is
+ * added into wsum [B,Ha,Wa] f32.  weighting 0: weight 1;  1: Gaussian, expf(-(dy^2 / (2 sy^2) + dx^2 / (2 sx^2))) with
+ * dy = ly - (ch - 1) / 2, sy = ch / 8 and likewise in x, fp32 (at least e^-16: wsum is never 0 on a covered pixel).
+ * The sum is a gather over accumulator pixels: each pixel adds the windows that cover it in TABLE ORDER, onto the
+ * value the accumulator holds, in fp32 with every product and sum rounded on its own.  No atomics, one writer per
+ * address: the result is deterministic, and bitwise the same however the window list is cut into calls.
+ * windows: device table; windows_host: the same rows in host memory, checked here: 1 <= n <= 64, 1 <= C <= 64, and
+ * every non-null window has 0 <= b < B and lies inside the accumulator frame (else SSSEG_EINVAL). */
+int ssseg_window_accumulate(const float* logits, const int64_t* logit_strides4, int64_t n, int64_t C, int64_t h,
+                            int64_t w, const int32_t* windows, const int32_t* windows_host, int64_t ch, int64_t cw,
+                            int activation, int weighting, float* acc, float* wsum, int64_t B, int64_t Ha, int64_t Wa,
+                            ssseg_stream_t stream);
+
+/* out [B,C,H,W] f32 (contiguous) = (first != 0) or += (first == 0) scale_weight * bilinear(acc / wsum), sampled from
+ * the [Hs,Ws] interior (top left) of acc [B,C,Ha,Wa] / wsum [B,Ha,Wa]; each tap is divided by its own wsum before the
+ * interpolation.  Where Hs == H and Ws == W the value is exactly acc / wsum * scale_weight.  1 <= C <= 64. */
+int ssseg_window_merge(const float* acc, const float* wsum, int64_t B, int64_t C, int64_t Ha, int64_t Wa, int64_t Hs,
+                       int64_t Ws, float* out, int64_t H, int64_t W, float scale_weight, int first,
+                       ssseg_stream_t stream);
+
+/* labels [B,HW] int64 = argmax over the C channels of x [B,C,HW] f32 (contiguous): torch.argmax's rule, the first
+ * maximum wins and NaN counts as the maximum.  1 <= C <= 64. */
+int ssseg_window_argmax(const float* x, int64_t B, int64_t C, int64_t HW, int64_t* labels, ssseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Collectives: the data-parallel gradient all-reduce and the SyncBN sums
  * (reference distributed_trainer.py:34-38 -- SyncBatchNorm.convert_sync_batchnorm + DistributedDataParallel,
  * whose reducer all-reduces gradient buckets during backward; SyncBN all-reduces per-channel sums)

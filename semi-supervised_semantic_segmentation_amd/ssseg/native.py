@@ -217,6 +217,12 @@ SIGS = {
     'ssseg_rng_take': (i32, [vp, vp, u64, vp]),
     'ssseg_att_blend_fwd': (i32, [vp, I64P, vp, I64P, vp, I64P, vp, i64, i64, i64, i64, vp]),
     'ssseg_att_blend_bwd': (i32, [vp, I64P, vp, I64P, vp, I64P, vp, I64P, vp, vp, vp, i64, i64, i64, i64, vp]),
+    # sliding-window evaluation (csrc/sliding.hip; ssseg/sliding.py)
+    'ssseg_window_gather': (i32, [vp, I64P, i64, i64, i64, i64, vp, i64, vp, I64P, i64, i64, i32, vp]),
+    'ssseg_window_accumulate': (i32, [vp, I64P, i64, i64, i64, i64, vp, vp, i64, i64, i32, i32, vp, vp, i64, i64, i64,
+                                      vp]),
+    'ssseg_window_merge': (i32, [vp, vp, i64, i64, i64, i64, i64, i64, vp, i64, i64, f32, i32, vp]),
+    'ssseg_window_argmax': (i32, [vp, i64, i64, i64, vp, vp]),
     # collectives (csrc/comm.hip; ssseg/comm.py)
     'ssseg_comm_unique_id_bytes': (sz, []),
     'ssseg_comm_get_unique_id': (i32, [vp]),

@@ -24,6 +24,7 @@ import utils.utils as utils
 from ssseg import nn as snn
 from ssseg import ops
 from ssseg import param_step
+from ssseg import sliding
 from ssseg.ddp import DistributedDataParallel as _DDP
 from ssseg.optim import SGD as _SGD, FusedOptimizer as _Fused
 
@@ -620,8 +621,13 @@ def validate(model, dataloader, epoch, initial_step, summary_writer, config, dev
     whole validation set (lovasz.iou, lovasz.py:54-73) from the same device pass (ssseg_seg_metrics; a mask with other
     than 2 channels takes ssseg_seg_metrics_mc with num_classes from the mask, and logs the per-class IoUs too).
     A [B, H, W] label map (uint8 / int64) takes ssseg_seg_metrics_mc too, with the class count from the prediction's
-    channels and config['train'].get('ignore_label') as the void label, left out of every count."""
+    channels and config['train'].get('ignore_label') as the void label, left out of every count.
+    With config['val']['sliding_window'] = dict(crop_size=, stride=, scales=, flip=, weighting=, window_batch=) the
+    prediction is the fused logit map of ssseg.sliding.SlidingWindowInference (activation 'none') at the image's own
+    size, in the place of the single whole-image forward; the loss and the metrics take it where pred_maps[-1] goes."""
     model.eval()
+    sw = (config.get('val') or {}).get('sliding_window')
+    fuse = sliding.SlidingWindowInference(model, activation='none', **sw) if sw else None
     avg_loss, avg_metric = utils.AverageMeter(), utils.AverageMeter()
     rank = torch.distributed.get_rank() if torch.distributed.is_initialized() else 0
     world = _world()
@@ -630,7 +636,10 @@ def validate(model, dataloader, epoch, initial_step, summary_writer, config, dev
         for sample in dataloader:
             image = sample['image'].to(device)
             mask = sample['semantic_mask'].to(device)
-            features, pred_maps = model(image)
+            if fuse is not None:
+                pred_maps = [fuse(image)]
+            else:
+                features, pred_maps = model(image)
             if seg is None and mask.dim() == 3:
                 # a label map: the C-class kernel, with the class count from the prediction and the void label left out
                 seg = ops.SegMetricsMC(device, pred_maps[-1].shape[1], config['train'].get('ignore_label'))
