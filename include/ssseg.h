@@ -1211,6 +1211,41 @@ int ssseg_window_merge(const float* acc, const float* wsum, int64_t B, int64_t C
 int ssseg_window_argmax(const float* x, int64_t B, int64_t C, int64_t HW, int64_t* labels, ssseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Post-training int8 inference (csrc/quant.hip; ssseg/quant.py).  Replaces the reference's inference.py
+ * (torch.quantization prepare / convert on fbgemm).  The scheme, fixed so that a host restatement agrees bit for bit:
+ *   weights      symmetric int8 per output channel on the raw conv weight: aw[k] = max |w[k]|, sw[k] = aw[k] / 127.0f,
+ *                qw = clamp(rint(w * (127.0f / aw[k])), -127, 127), ties to even; aw[k] == 0 -> sw[k] = 0, qw = 0
+ *   activations  symmetric int8 per tensor at the conv's input: a = running max of finite |x| over calibration (slot),
+ *                sx = a / 127.0f, q = clamp(rint(float(x) * (127.0f / a)), -127, 127); a == 0 -> 0, NaN -> 0,
+ *                +-Inf -> +-127
+ *   conv         acc = sum q * qw in int32 (exact);  m[k] = (sx * sw[k]) * scale[k] (scale NULL = 1), in that fp32 order;
+ *                y = act(fmaf(float(acc), m[k], shift[k]) + residual), every operation rounded to fp32 on its own
+ * Every scale lives on the device: no entry point synchronises, all are graph-capturable.  NULL pointers are
+ * SSSEG_EINVAL, checked on the host before any launch.
+ * ------------------------------------------------------------------------------------------- */
+/* slot[0] = max(slot[0], max over p < P, c < C of |x[p*ldx + c]| over the finite values); channels C <= c < ldx are
+ * never read.  x: dtype dt (SSSEG_F32 / BF16 / F16).  Bitwise the fp32 amax (an integer atomic max on the bits). */
+int ssseg_absmax_update(const void* x, int64_t P, int64_t C, int64_t ldx, int dt, float* slot, ssseg_stream_t stream);
+/* q[p*ldq + c] = the scheme's int8 of x[p*ldx + c] for c < C and 0 for C <= c < ldq; ldq == rup(C, 16), q 16-byte
+ * aligned.  Input channels >= C are never read. */
+int ssseg_quantize_i8(const void* x, int64_t P, int64_t C, int64_t ldx, int dt, const float* slot, int8_t* q,
+                      int64_t ldq, ssseg_stream_t stream);
+/* w [K][C][R][S] fp32 (the master weight) -> qw [Kp][R][S][Cq] int8 and sw [Kp] fp32; rows K <= k < Kp and channels
+ * C <= c < Cq are zeros.  Kp >= K, Cq >= C, Cq % 16 == 0. */
+int ssseg_weight_quant_i8(const float* w, int64_t K, int64_t C, int64_t R, int64_t S, int64_t Kp, int64_t Cq,
+                          int8_t* qw, float* sw, ssseg_stream_t stream);
+/* Forward conv on v_mfma_i32_16x16x64_i8: implicit GEMM, M = N*OH*OW, N = desc->K, contraction R*S*desc->C.
+ * q: int8 NHWC, desc->C channels (% 16 == 0; ssseg_quantize_i8's ldq) at pixel stride desc->ldx; qw / sw from
+ * ssseg_weight_quant_i8 with Cq = desc->C and Kp = rup(desc->K, 16) (desc->ldw == R*S*C); y: dtype dt_out (SSSEG_F32 /
+ * BF16 / F16) at pixel stride desc->ldy; epi (may be NULL) gives scale / shift (desc->K floats), residual (dtype
+ * dt_out, pixel stride ldr) and the activation; epi->aux and epi->stats must be NULL (SSSEG_EINVAL).
+ * Covers 1 <= R, S <= 7, stride 1 and 2, any dilation >= 1, zero padding (py, px <= 0 offsets as in the 16-bit engine),
+ * desc->K >= 8 in steps of 8, the dense output map (outH == OH, outW == OW, osy == osx == 1, ooy == oox == 0);
+ * SSSEG_EUNSUPPORTED otherwise. */
+int ssseg_conv_i8_fwd(const int8_t* q, const int8_t* qw, void* y, const ssseg_conv_desc* desc_host, int dt_out,
+                      const float* slot, const float* sw, const ssseg_conv_epilogue* epi, ssseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Collectives: the data-parallel gradient all-reduce and the SyncBN sums
  * (reference distributed_trainer.py:34-38 -- SyncBatchNorm.convert_sync_batchnorm + DistributedDataParallel,
  * whose reducer all-reduces gradient buckets during backward; SyncBN all-reduces per-channel sums)

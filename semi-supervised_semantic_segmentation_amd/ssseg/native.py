@@ -223,6 +223,11 @@ SIGS = {
                                       vp]),
     'ssseg_window_merge': (i32, [vp, vp, i64, i64, i64, i64, i64, i64, vp, i64, i64, f32, i32, vp]),
     'ssseg_window_argmax': (i32, [vp, i64, i64, i64, vp, vp]),
+    # post-training int8 inference (csrc/quant.hip; ssseg/quant.py)
+    'ssseg_absmax_update': (i32, [vp, i64, i64, i64, i32, vp, vp]),
+    'ssseg_quantize_i8': (i32, [vp, i64, i64, i64, i32, vp, vp, i64, vp]),
+    'ssseg_weight_quant_i8': (i32, [vp, i64, i64, i64, i64, i64, i64, vp, vp, vp]),
+    'ssseg_conv_i8_fwd': (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp]),
     # collectives (csrc/comm.hip; ssseg/comm.py)
     'ssseg_comm_unique_id_bytes': (sz, []),
     'ssseg_comm_get_unique_id': (i32, [vp]),

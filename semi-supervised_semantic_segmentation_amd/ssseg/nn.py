@@ -29,6 +29,10 @@ _CFG = {'act_mask': os.environ.get('SSSEG_ACT_MASK', '1') != '0',
         'bn_join': os.environ.get('SSSEG_BN_JOIN', '1') != '0'}
 
 
+# the active ssseg.quant context's per-conv hook (None outside calibrating() / quantized(): nothing changes there)
+_QUANT = [None]
+
+
 def set_bn_grad_stats(on):
     """A training BN(+ReLU) whose output feeds exactly one conv (conv_bn_act(..., single_use=True)): that conv's
     input-gradient launch applies the ReLU backward and writes the BN backward's two channel sums in its epilogue
@@ -796,6 +800,9 @@ class _ConvBase:
         self._ssseg_packs = {}
         self._ssseg_specs = {}
         _PACK_EPOCH[0] += 1
+        rec = self.__dict__.get('_ssseg_q')
+        if rec is not None:
+            rec.drop()
 
     def _pack(self, key, Kd, Kr, Cd, Cp, layout, r0, rstep, Rn, s0, sstep, Sn):
         key = (key, _CFG['dtype'], Cp)
@@ -993,6 +1000,11 @@ class Conv2d(nn.Conv2d, _ConvBase):
     def _ssseg_forward(self, x, relu, bn=None, residual=None, keep_pre=False, stats=None, aux_copy=True):
         cin, cout = self._dims()
         _need_act(x, cin, 'Conv2d')
+        if _QUANT[0] is not None and not keep_pre and stats is None and not torch.is_grad_enabled():
+            # inside ssseg.quant.calibrating / quantized: observe the input, or run the int8 kernels
+            y = _QUANT[0](self, x, relu, bn, residual)
+            if y is not None:
+                return y
         if self._ssseg_dw:
             if stats is not None:
                 raise NotImplementedError('ssseg: fused BN statistics on a depthwise conv')
@@ -1989,7 +2001,10 @@ def invalidate_packed(model):
     device descriptor table is cached on the model and rebuilt only when the set of packs changes; while
     no conv gained or dropped a pack (_PACK_EPOCH) and every master weight still has the same storage, the
     cached tables are relaunched without walking the module tree (the walk cost ~0.2 ms of host time per
-    model per step)."""
+    model per step).  The int8 weights and frozen folds of ssseg.quant are derived from the same parameters: they are
+    dropped here (host bookkeeping only) and re-derived by the next quantised forward."""
+    for rec in model.__dict__.get('_ssseg_quant_recs', ()):
+        rec.drop()
     fast = model.__dict__.get('_ssseg_pack_fast')
     if fast is not None and fast[0] == _PACK_EPOCH[0] and all(
             m.weight is w and w.data_ptr() == ptr for m, w, ptr in fast[1]):
