@@ -14,24 +14,9 @@
 // albumentations and cv2 are absent from this image: parity with them is unpinned; the kernels are checked against
 // the numpy restatement in oracle/augment_ref.py (tests/test_augment.py).
 #include "common.h"
+#include "philox.h"
 
 namespace {
-
-__device__ __forceinline__ void philox(unsigned (&c)[4], uint64_t seed) {
-  unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
-    const unsigned hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0];
-    const unsigned hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
-    const unsigned n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-    c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
-// uniform in (0, 1]
-__device__ __forceinline__ float u01(unsigned v) { return ((float)(v >> 8) + 1.0f) * (1.0f / 16777216.0f); }
 
 // reflect-101 (OpenCV BORDER_REFLECT_101: ... c b | a b c ... | d c ...) and scipy 'reflect' (... b a | a b ...)
 __device__ __forceinline__ int reflect101(int i, int n) {
@@ -314,9 +299,10 @@ __global__ void aug_iso_finish_kernel(const float* __restrict__ img, float* __re
     const float* px = img + ((int64_t)n * HW + i) * 3;
     float r = px[0], g = px[1], b = px[2];
     if (p.iso) {
+      // (the blocks here are initialised in place, not through philox_block: that form changes these kernels' code)
       unsigned c[4] = {(unsigned)i, (unsigned)(i >> 32), (unsigned)n, 0x150u};
-      philox(c, seed);
-      const float u1 = u01(c[0]), u2 = u01(c[1]), u3 = u01(c[2]);
+      philox4x32_10(c, seed);
+      const float u1 = philox_u01_upper(c[0]), u2 = philox_u01_upper(c[1]), u3 = philox_u01_upper(c[2]);
       const float nrm = sqrtf(-2.f * logf(u1)) * cosf(6.2831853f * u2);
       float h, l, s;
       rgb2hls(r / 255.f, g / 255.f, b / 255.f, h, l, s);
@@ -340,8 +326,8 @@ __global__ void aug_iso_finish_kernel(const float* __restrict__ img, float* __re
 __global__ void aug_uniform_field_kernel(float* __restrict__ f, int64_t total, uint64_t seed) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     unsigned c[4] = {(unsigned)i, (unsigned)(i >> 32), 0xe1a5u, 0u};
-    philox(c, seed);
-    f[i] = u01(c[0]) * 2.f - 1.f;
+    philox4x32_10(c, seed);
+    f[i] = philox_u01_upper(c[0]) * 2.f - 1.f;
   }
 }
 

@@ -28,56 +28,6 @@ constexpr int CH = 4;   // ABI granularity: every leading dimension is a multipl
 
 static inline bool ld_bad(int64_t C, int64_t ld) { return ld % CH != 0 || ld < (C + CH - 1) / CH * CH; }
 
-template <typename T, int V> struct Vec;
-template <> struct Vec<float, 4> {
-  __device__ __forceinline__ static void ld(const float* p, float (&v)[4]) {
-    const float4 q = *(const float4*)p;
-    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-  }
-  __device__ __forceinline__ static void st(float* p, const float (&v)[4]) { *(float4*)p = make_float4(v[0], v[1], v[2], v[3]); }
-};
-template <> struct Vec<float, 2> {
-  __device__ __forceinline__ static void ld(const float* p, float (&v)[2]) {
-    const float2 q = *(const float2*)p;
-    v[0] = q.x; v[1] = q.y;
-  }
-  __device__ __forceinline__ static void st(float* p, const float (&v)[2]) { *(float2*)p = make_float2(v[0], v[1]); }
-};
-__device__ __forceinline__ void unpack2(unsigned u, float& a, float& b) {
-  a = __uint_as_float(u << 16);
-  b = __uint_as_float(u & 0xffff0000u);
-}
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-  return (unsigned)f32_to_bf16(a) | ((unsigned)f32_to_bf16(b) << 16);
-}
-template <> struct Vec<bf16_t, 8> {
-  __device__ __forceinline__ static void ld(const bf16_t* p, float (&v)[8]) {
-    const uint4 q = *(const uint4*)p;
-    unpack2(q.x, v[0], v[1]); unpack2(q.y, v[2], v[3]); unpack2(q.z, v[4], v[5]); unpack2(q.w, v[6], v[7]);
-  }
-  __device__ __forceinline__ static void st(bf16_t* p, const float (&v)[8]) {
-    *(uint4*)p = make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
-  }
-};
-template <> struct Vec<bf16_t, 4> {
-  __device__ __forceinline__ static void ld(const bf16_t* p, float (&v)[4]) {
-    const uint2 q = *(const uint2*)p;
-    unpack2(q.x, v[0], v[1]); unpack2(q.y, v[2], v[3]);
-  }
-  __device__ __forceinline__ static void st(bf16_t* p, const float (&v)[4]) {
-    *(uint2*)p = make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
-  }
-};
-
-template <> struct Vec<f16_t, 8> {
-  __device__ __forceinline__ static void ld(const f16_t* p, float (&v)[8]) { H16::ld8(p, v); }
-  __device__ __forceinline__ static void st(f16_t* p, const float (&v)[8]) { H16::st8(p, v); }
-};
-template <> struct Vec<f16_t, 4> {
-  __device__ __forceinline__ static void ld(const f16_t* p, float (&v)[4]) { H16::ld4(p, v); }
-  __device__ __forceinline__ static void st(f16_t* p, const float (&v)[4]) { H16::st4(p, v); }
-};
-
 struct Layout {
   int cpb;        // chunks per block row (<= 256)
   int ppb;        // pixel rows per block

@@ -58,43 +58,18 @@ template <> struct io<f16_t> {
   __device__ __forceinline__ static void st(f16_t* p, int64_t i, float v) { p[i] = (f16_t)v; }
 };
 
-// 16-byte (8 x fp16) and 8-byte (4 x fp16) vector loads/stores with fp32 values: the fp16 member of the
-// per-file 16-byte chunk helpers (bf16 and fp32 have their own)
-struct H16 {
-  __device__ __forceinline__ static void ld8(const f16_t* p, float (&v)[8]) {
-    const uint4 q = *(const uint4*)p;
-    const unsigned w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const f16x2_t h = __builtin_bit_cast(f16x2_t, w[i]);
-      v[2 * i] = (float)h[0];
-      v[2 * i + 1] = (float)h[1];
-    }
-  }
-  __device__ __forceinline__ static void st8(f16_t* p, const float (&v)[8]) {
-    unsigned w[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const f16x2_t h = {(f16_t)v[2 * i], (f16_t)v[2 * i + 1]};
-      w[i] = __builtin_bit_cast(unsigned, h);
-    }
-    *(uint4*)p = make_uint4(w[0], w[1], w[2], w[3]);
-  }
-  __device__ __forceinline__ static void ld4(const f16_t* p, float (&v)[4]) {
-    const uint2 q = *(const uint2*)p;
-    const f16x2_t a = __builtin_bit_cast(f16x2_t, q.x), b = __builtin_bit_cast(f16x2_t, q.y);
-    v[0] = (float)a[0]; v[1] = (float)a[1]; v[2] = (float)b[0]; v[3] = (float)b[1];
-  }
-  __device__ __forceinline__ static void st4(f16_t* p, const float (&v)[4]) {
-    const f16x2_t a = {(f16_t)v[0], (f16_t)v[1]}, b = {(f16_t)v[2], (f16_t)v[3]};
-    *(uint2*)p = make_uint2(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b));
-  }
-};
+// two fp32 values rounded to one dword of bf16 (low half first); pairwise, so that the compiler picks the packed
+// conversion (v_cvt_pk_bf16_f32)
+__device__ __forceinline__ unsigned bf16x2_bits(float a, float b) {
+  return (unsigned)f32_to_bf16(a) | ((unsigned)f32_to_bf16(b) << 16);
+}
 
-// Raw V-element chunks (16 or 8 bytes): ld() moves the bits only, cvt() converts to fp32 later.  Streaming
+// Raw V-element chunks (16 or 8 bytes): ld() moves the bits only, cvt() converts to fp32 later and pack() is its
+// inverse, in registers (for the sites that shuffle or stage the packed bits before they store them).  Streaming
 // kernels issue every load of a batch first (clamped addresses, no branch around a load) and convert after,
 // so the batch is in flight together: a conversion right behind each conditional load makes the compiler
 // wait for that load (s_waitcnt vmcnt(0)) before issuing the next, serialising the memory round trips.
+// These, Vec below, philox.h and Strides4 are the only copies of their kind: a kernel file defines none of its own.
 template <typename T, int V> struct Chunk;
 template <> struct Chunk<bf16_t, 8> {
   typedef uint4 raw;
@@ -108,6 +83,12 @@ template <> struct Chunk<bf16_t, 8> {
       v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
     }
   }
+  __device__ __forceinline__ static raw pack(const float (&v)[8]) {
+    unsigned w[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) w[i] = bf16x2_bits(v[2 * i], v[2 * i + 1]);
+    return make_uint4(w[0], w[1], w[2], w[3]);
+  }
 };
 template <> struct Chunk<bf16_t, 4> {
   typedef uint2 raw;
@@ -116,6 +97,10 @@ template <> struct Chunk<bf16_t, 4> {
   __device__ __forceinline__ static void cvt(const raw& q, float (&v)[4]) {
     v[0] = __uint_as_float(q.x << 16); v[1] = __uint_as_float(q.x & 0xffff0000u);
     v[2] = __uint_as_float(q.y << 16); v[3] = __uint_as_float(q.y & 0xffff0000u);
+  }
+  __device__ __forceinline__ static raw pack(const float (&v)[4]) {
+    const unsigned a = bf16x2_bits(v[0], v[1]), b = bf16x2_bits(v[2], v[3]);
+    return make_uint2(a, b);
   }
 };
 template <> struct Chunk<f16_t, 8> {
@@ -131,6 +116,15 @@ template <> struct Chunk<f16_t, 8> {
       v[2 * i + 1] = (float)h[1];
     }
   }
+  __device__ __forceinline__ static raw pack(const float (&v)[8]) {
+    unsigned w[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const f16x2_t h = {(f16_t)v[2 * i], (f16_t)v[2 * i + 1]};
+      w[i] = __builtin_bit_cast(unsigned, h);
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+  }
 };
 template <> struct Chunk<f16_t, 4> {
   typedef uint2 raw;
@@ -140,6 +134,10 @@ template <> struct Chunk<f16_t, 4> {
     const f16x2_t a = __builtin_bit_cast(f16x2_t, q.x), b = __builtin_bit_cast(f16x2_t, q.y);
     v[0] = (float)a[0]; v[1] = (float)a[1]; v[2] = (float)b[0]; v[3] = (float)b[1];
   }
+  __device__ __forceinline__ static raw pack(const float (&v)[4]) {
+    const f16x2_t a = {(f16_t)v[0], (f16_t)v[1]}, b = {(f16_t)v[2], (f16_t)v[3]};
+    return make_uint2(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b));
+  }
 };
 template <> struct Chunk<float, 4> {
   typedef float4 raw;
@@ -148,6 +146,7 @@ template <> struct Chunk<float, 4> {
   __device__ __forceinline__ static void cvt(const raw& q, float (&v)[4]) {
     v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
   }
+  __device__ __forceinline__ static raw pack(const float (&v)[4]) { return make_float4(v[0], v[1], v[2], v[3]); }
 };
 template <> struct Chunk<float, 2> {
   typedef float2 raw;
@@ -156,7 +155,41 @@ template <> struct Chunk<float, 2> {
   __device__ __forceinline__ static void cvt(const raw& q, float (&v)[2]) {
     v[0] = q.x; v[1] = q.y;
   }
+  __device__ __forceinline__ static raw pack(const float (&v)[2]) { return make_float2(v[0], v[1]); }
 };
+template <> struct Chunk<float, 1> {   // the scalar member, for kernels templated on the vector width
+  typedef float raw;
+  __device__ __forceinline__ static raw ld(const float* p) { return *p; }
+  __device__ __forceinline__ static raw zero() { return 0.f; }
+  __device__ __forceinline__ static void cvt(const raw& q, float (&v)[1]) { v[0] = q; }
+  __device__ __forceinline__ static raw pack(const float (&v)[1]) { return v[0]; }
+};
+
+// N consecutive elements at p (aligned to the chunk) as fp32 values: one load and convert, or pack and one store
+template <typename T, int N> struct Vec {
+  static constexpr int V = N;
+  using CK = Chunk<T, N>;
+  __device__ __forceinline__ static void ld(const T* p, float (&v)[N]) { CK::cvt(CK::ld(p), v); }
+  __device__ __forceinline__ static void st(T* p, const float (&v)[N]) { *(typename CK::raw*)p = CK::pack(v); }
+};
+template <> struct Vec<float, 8> {   // two 16-byte accesses
+  static constexpr int V = 8;
+  __device__ __forceinline__ static void ld(const float* p, float (&v)[8]) {
+    const float4 a = *(const float4*)p, b = *(const float4*)(p + 4);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+  }
+  __device__ __forceinline__ static void st(float* p, const float (&v)[8]) {
+    *(float4*)p = make_float4(v[0], v[1], v[2], v[3]);
+    *(float4*)(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
+  }
+};
+template <typename T> using Vec16 = Vec<T, 16 / sizeof(T)>;   // the 16-byte chunk of T: 8 x bf16 / fp16, 4 x fp32
+
+// element strides of a 4-D tensor, as the entries receive them
+struct Strides4 {
+  int64_t n, c, h, w;
+};
+static inline Strides4 strides4(const int64_t* s) { return Strides4{s[0], s[1], s[2], s[3]}; }
 
 // wave64 reductions
 __device__ __forceinline__ float wave_sum(float v) {

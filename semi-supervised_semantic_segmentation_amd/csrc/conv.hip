@@ -175,7 +175,7 @@ __global__ void __launch_bounds__(256) weight_pack_batch_kernel(const ssseg_pack
       for (int e = 0; e < 8; ++e) v[e] = lds[(kk * CC + c8 * 8 + e) * RSP + t];
       const int o = (k * taps + tt) * Cp + c;
       if (c + 8 <= Cp && (Cp & 7) == 0) {
-        Out8<T>::st(dst + o, v);
+        Vec<T, 8>::st(dst + o, v);
       } else {
 #pragma unroll
         for (int e = 0; e < 8; ++e)

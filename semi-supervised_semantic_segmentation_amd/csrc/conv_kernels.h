@@ -149,22 +149,6 @@ template <> struct MF<float> {
   }
 };
 
-template <typename TO> struct Store4;
-template <> struct Store4<float> {
-  __device__ __forceinline__ static void st(float* p, const float (&v)[4]) { *(float4*)p = make_float4(v[0], v[1], v[2], v[3]); }
-};
-template <> struct Store4<f16_t> {
-  __device__ __forceinline__ static void st(f16_t* p, const float (&v)[4]) { H16::st4(p, v); }
-};
-template <> struct Store4<bf16_t> {
-  __device__ __forceinline__ static void st(bf16_t* p, const float (&v)[4]) {
-    uint2 u;
-    u.x = (unsigned)f32_to_bf16(v[0]) | ((unsigned)f32_to_bf16(v[1]) << 16);
-    u.y = (unsigned)f32_to_bf16(v[2]) | ((unsigned)f32_to_bf16(v[3]) << 16);
-    *(uint2*)p = u;
-  }
-};
-
 // epilogue: y = act(acc * scale[n] + shift[n] + res[pixel][n]); scale null = 1, shift null = 0
 // (conv bias -> shift; a folded eval BatchNorm -> scale/shift; Bottleneck identity -> res)
 template <typename TO>
@@ -275,24 +259,6 @@ struct PhaseTab {
   const void* w[4];
 };
 
-template <typename TO> struct Load4;
-template <> struct Load4<float> {
-  __device__ __forceinline__ static void ld(const float* p, float (&v)[4]) {
-    const float4 q = *(const float4*)p;
-    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-  }
-};
-template <> struct Load4<f16_t> {
-  __device__ __forceinline__ static void ld(const f16_t* p, float (&v)[4]) { H16::ld4(p, v); }
-};
-template <> struct Load4<bf16_t> {
-  __device__ __forceinline__ static void ld(const bf16_t* p, float (&v)[4]) {
-    const uint2 q = *(const uint2*)p;
-    v[0] = __uint_as_float(q.x << 16); v[1] = __uint_as_float(q.x & 0xffff0000u);
-    v[2] = __uint_as_float(q.y << 16); v[3] = __uint_as_float(q.y & 0xffff0000u);
-  }
-};
-
 // Writes one wave's FN x FM fragments: y[pixel(m)][n..n+3] = act(acc*scale + shift + res), NHWC.
 // The per-channel affine of a fragment column is loaded once, and every residual of the column is loaded
 // before the first store (the stores may alias the residual as far as the compiler knows, so it could not
@@ -329,7 +295,7 @@ __device__ __forceinline__ void store_tile(const f32x4 (&acc)[FN][FM], long long
       if (ep.res && op[j] >= 0 && n < ep.oc1) {
         const TO* rp = ep.res + op[j] * ep.ldr + n;
         if (full && (ep.ldr & 3) == 0)
-          Load4<TO>::ld(rp, r[j]);
+          Vec<TO, 4>::ld(rp, r[j]);
         else
 #pragma unroll
           for (int e = 0; e < 4; ++e)   // fixed trip count: r stays in registers (a runtime bound spills it)
@@ -344,7 +310,7 @@ __device__ __forceinline__ void store_tile(const f32x4 (&acc)[FN][FM], long long
         if (op[j] >= 0) {
           const TO* zp = ep.zmask + op[j] * ep.ldz + n;
           if (full && (ep.ldz & 3) == 0)
-            Load4<TO>::ld(zp, z);
+            Vec<TO, 4>::ld(zp, z);
           else
 #pragma unroll
             for (int e = 0; e < 4; ++e)
@@ -359,7 +325,7 @@ __device__ __forceinline__ void store_tile(const f32x4 (&acc)[FN][FM], long long
       if (ep.aux) {
         const float a4[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
         if (full && (g.ldy & 3) == 0)
-          Store4<TO>::st(ep.aux + op[j] * g.ldy + n, a4);
+          Vec<TO, 4>::st(ep.aux + op[j] * g.ldy + n, a4);
         else
 #pragma unroll
           for (int e = 0; e < 4; ++e)
@@ -394,7 +360,7 @@ __device__ __forceinline__ void store_tile(const f32x4 (&acc)[FN][FM], long long
       }
       TO* yp = out_at(ep, y, g.ldy, op[j], n);
       if (full && (g.ldy & 3) == 0) {
-        Store4<TO>::st(yp, v);
+        Vec<TO, 4>::st(yp, v);
       } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e)
@@ -421,39 +387,6 @@ __device__ __forceinline__ void act8(float (&v)[8], int act, float slope) {
     for (int e = 0; e < 8; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * slope;
   }
 }
-
-template <typename TO> struct Out8;
-template <> struct Out8<bf16_t> {
-  __device__ __forceinline__ static void ld(const bf16_t* p, float (&v)[8]) {
-    const uint4 q = *(const uint4*)p;
-    const unsigned w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      v[2 * i] = __uint_as_float(w[i] << 16);
-      v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
-  }
-  __device__ __forceinline__ static void st(bf16_t* p, const float (&v)[8]) {
-    unsigned w[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w[i] = (unsigned)f32_to_bf16(v[2 * i]) | ((unsigned)f32_to_bf16(v[2 * i + 1]) << 16);
-    *(uint4*)p = make_uint4(w[0], w[1], w[2], w[3]);
-  }
-};
-template <> struct Out8<f16_t> {
-  __device__ __forceinline__ static void ld(const f16_t* p, float (&v)[8]) { H16::ld8(p, v); }
-  __device__ __forceinline__ static void st(f16_t* p, const float (&v)[8]) { H16::st8(p, v); }
-};
-template <> struct Out8<float> {
-  __device__ __forceinline__ static void ld(const float* p, float (&v)[8]) {
-    const float4 a = *(const float4*)p, b = *(const float4*)(p + 4);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-  }
-  __device__ __forceinline__ static void st(float* p, const float (&v)[8]) {
-    *(float4*)p = make_float4(v[0], v[1], v[2], v[3]);
-    *(float4*)(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
-  }
-};
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 template <int NP> struct PreRes {   // residual chunks an epilogue thread loaded ahead of the main loop
@@ -641,10 +574,10 @@ __device__ __forceinline__ void store_tile_lds(const f32x4 (&acc)[FN][FM], char*
               const u32x4 q = pre.v[p < NPRE ? p : 0];
               Chunk<TO, 8>::cvt(make_uint4(q.x, q.y, q.z, q.w), r[JOIN ? 0 : p]);
             } else {
-              Out8<TO>::ld(ep.res + op[p] * ep.ldr + n, r[JOIN ? 0 : p]);
+              Vec<TO, 8>::ld(ep.res + op[p] * ep.ldr + n, r[JOIN ? 0 : p]);
             }
           } else {
-            Out8<TO>::ld(ep.res + op[p] * ep.ldr + n, r[JOIN ? 0 : p]);
+            Vec<TO, 8>::ld(ep.res + op[p] * ep.ldr + n, r[JOIN ? 0 : p]);
           }
         } else
 #pragma unroll
@@ -702,8 +635,8 @@ __device__ __forceinline__ void store_tile_lds(const f32x4 (&acc)[FN][FM], char*
       const long long o = op[p] * g.ldy + n;
       TO* yp = out_at(ep, y, g.ldy, op[p], n);   // (a split output has no aux: host contract)
       if (full) {
-        Out8<TO>::st(yp, v);
-        if (ep.aux) Out8<TO>::st(ep.aux + o, raw);
+        Vec<TO, 8>::st(yp, v);
+        if (ep.aux) Vec<TO, 8>::st(ep.aux + o, raw);
       } else {
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
@@ -1419,7 +1352,7 @@ __global__ void phase_zero_vec_kernel(TO* y, ConvGeom g, Epi<TO> ep) {
     const long long m = i / kc;
     const long long op = out_pixel(g, (int)m);   // M < 2^31 (geom_ok)
     float r[8], v[8];
-    if (ep.res && !ep.rmask) Out8<TO>::ld(ep.res + op * ep.ldr + n, r);
+    if (ep.res && !ep.rmask) Vec<TO, 8>::ld(ep.res + op * ep.ldr + n, r);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       float t = ep.shift ? ep.shift[n + e] : 0.f;
@@ -1428,9 +1361,9 @@ __global__ void phase_zero_vec_kernel(TO* y, ConvGeom g, Epi<TO> ep) {
     }
     if (ep.aux) {
       const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      Out8<TO>::st(ep.aux + op * g.ldy + n, z);
+      Vec<TO, 8>::st(ep.aux + op * g.ldy + n, z);
     }
-    Out8<TO>::st(out_at(ep, y, g.ldy, op, n), v);
+    Vec<TO, 8>::st(out_at(ep, y, g.ldy, op, n), v);
   }
 }
 

@@ -38,20 +38,6 @@ __device__ __forceinline__ void act4(float (&v)[4], int act, float slope) {
   }
 }
 
-template <typename TO> struct Pack4;
-template <> struct Pack4<bf16_t> {
-  __device__ __forceinline__ static uint2 pk(const float (&v)[4]) {
-    return make_uint2((unsigned)f32_to_bf16(v[0]) | ((unsigned)f32_to_bf16(v[1]) << 16),
-                      (unsigned)f32_to_bf16(v[2]) | ((unsigned)f32_to_bf16(v[3]) << 16));
-  }
-};
-template <> struct Pack4<f16_t> {
-  __device__ __forceinline__ static uint2 pk(const float (&v)[4]) {
-    const f16x2_t a = {(f16_t)v[0], (f16_t)v[1]}, b = {(f16_t)v[2], (f16_t)v[3]};
-    return make_uint2(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b));
-  }
-};
-
 // odd 16-lane rows of a <-> even rows of b
 __device__ __forceinline__ void swap16(uint2& a, uint2& b) {
   const auto x = __builtin_amdgcn_permlane16_swap(a.x, b.x, false, false);
@@ -198,13 +184,13 @@ __global__ void __launch_bounds__(256, 2) pw_kernel(const TO* __restrict__ x, co
           }
         }
         const long long o = ms * g.ldy + n0 + 16 * i + 8 * (lg >> 1);
-        uint2 a = Pack4<TO>::pk(v[0]), b = Pack4<TO>::pk(v[1]);
+        uint2 a = CK::pack(v[0]), b = CK::pack(v[1]);
         swap16(a, b);
         if (lives) *(uint4*)(y + o) = make_uint4(a.x, a.y, b.x, b.y);
         if (ep.aux) {
           const float r0[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
           const float r1[4] = {acc[i][j + 1][0], acc[i][j + 1][1], acc[i][j + 1][2], acc[i][j + 1][3]};
-          uint2 c = Pack4<TO>::pk(r0), d = Pack4<TO>::pk(r1);
+          uint2 c = CK::pack(r0), d = CK::pack(r1);
           swap16(c, d);
           if (lives) *(uint4*)(ep.aux + o) = make_uint4(c.x, c.y, d.x, d.y);
         }

@@ -8,6 +8,7 @@
 // order (k = 0..K-1), fp32 fused multiply-add.  HBM traffic: read noise, write+read tmp, write+read
 // field, write mask = 6 * 4 B per pixel (the field round trip is needed for the global statistics).
 #include "common.h"
+#include "philox.h"
 
 namespace {
 
@@ -243,38 +244,17 @@ __global__ void cowmix_threshold_kernel(const float* field, const float* thr, fl
 // ------------------------------------------------------------------------------------------------
 // Philox-4x32-10 normal(0,1) (Box-Muller) for throughput-mode noise.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox_round(unsigned (&c)[4], unsigned k0, unsigned k1) {
-  const unsigned M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
-  unsigned hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0];
-  unsigned hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
-  unsigned n0 = hi1 ^ c[1] ^ k0, n1 = lo1, n2 = hi0 ^ c[3] ^ k1, n3 = lo0;
-  c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
-
-// the Philox counter offset from device memory (graph-replayable draws: every replay reads the advanced counter) or
-// from the argument
-__device__ __forceinline__ uint64_t rng_offset(const unsigned long long* dev, uint64_t host, uint64_t add) {
-  return (dev ? (uint64_t)*dev : host) + add;
-}
-
 __global__ void normal_kernel(float* out, int64_t n, uint64_t seed, uint64_t offset,
                               const unsigned long long* offset_dev = nullptr, uint64_t add = 0) {
   offset = rng_offset(offset_dev, offset, add);
   for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q * 4 < n; q += (int64_t)gridDim.x * blockDim.x) {
-    const uint64_t ctr = offset + (uint64_t)q;
-    unsigned c[4] = {(unsigned)ctr, (unsigned)(ctr >> 32), 0u, 0u};
-    unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-      philox_round(c, k0, k1);
-      k0 += 0x9E3779B9u;
-      k1 += 0xBB67AE85u;
-    }
+    unsigned c[4];
+    philox_block(c, offset + (uint64_t)q, 0u);
+    philox4x32_10(c, seed);
     float z[4];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      const float u1 = ((float)(c[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-      const float u2 = (float)(c[2 * h + 1] >> 8) * (1.0f / 16777216.0f);
+      const float u1 = philox_u01_mid(c[2 * h]), u2 = philox_u01(c[2 * h + 1]);
       const float rad = sqrtf(-2.f * logf(u1));
       float s, co;
       sincosf(6.283185307179586f * u2, &s, &co);
@@ -293,15 +273,10 @@ __global__ void cowmix_draw_kernel(float* p, float* sigma, int B, float lo, floa
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   offset = rng_offset(offset_dev, offset, 0);
-  unsigned c[4] = {(unsigned)(offset + b), (unsigned)((offset + b) >> 32), 1u, 0u};
-  unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    philox_round(c, k0, k1);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  const float u1 = (float)(c[0] >> 8) * (1.0f / 16777216.0f), u2 = (float)(c[1] >> 8) * (1.0f / 16777216.0f);
+  unsigned c[4];
+  philox_block(c, offset + b, 1u);
+  philox4x32_10(c, seed);
+  const float u1 = philox_u01(c[0]), u2 = philox_u01(c[1]);
   p[b] = lo + u1 * (hi - lo);
   sigma[b] = expf(llo + u2 * (lhi - llo));
 }

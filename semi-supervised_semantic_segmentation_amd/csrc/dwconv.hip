@@ -13,39 +13,6 @@
 
 namespace {
 
-template <typename T> struct DV;
-template <> struct DV<bf16_t> {
-  static constexpr int V = 8;
-  __device__ __forceinline__ static void ld(const bf16_t* p, float (&v)[8]) {
-    const uint4 q = *(const uint4*)p;
-    const unsigned w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      v[2 * i] = __uint_as_float(w[i] << 16);
-      v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
-  }
-  __device__ __forceinline__ static void st(bf16_t* p, const float (&v)[8]) {
-    unsigned w[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w[i] = (unsigned)f32_to_bf16(v[2 * i]) | ((unsigned)f32_to_bf16(v[2 * i + 1]) << 16);
-    *(uint4*)p = make_uint4(w[0], w[1], w[2], w[3]);
-  }
-};
-template <> struct DV<f16_t> {
-  static constexpr int V = 8;
-  __device__ __forceinline__ static void ld(const f16_t* p, float (&v)[8]) { H16::ld8(p, v); }
-  __device__ __forceinline__ static void st(f16_t* p, const float (&v)[8]) { H16::st8(p, v); }
-};
-template <> struct DV<float> {
-  static constexpr int V = 4;
-  __device__ __forceinline__ static void ld(const float* p, float (&v)[4]) {
-    const float4 q = *(const float4*)p;
-    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-  }
-  __device__ __forceinline__ static void st(float* p, const float (&v)[4]) { *(float4*)p = make_float4(v[0], v[1], v[2], v[3]); }
-};
-
 struct DG {
   int N, H, W, C, ldx, OH, OW, R, S, sy, sx, dy, dx, py, px, ldy, ldw;
 };
@@ -55,7 +22,7 @@ __global__ void __launch_bounds__(256) dw_fwd_kernel(const T* __restrict__ x, co
                                                      DG g, const float* __restrict__ scale,
                                                      const float* __restrict__ shift, const T* __restrict__ res, int ldr,
                                                      T* __restrict__ aux, int act, float slope) {
-  constexpr int V = DV<T>::V;
+  constexpr int V = Vec16<T>::V;
   const int CV = g.C / V;
   const int total = g.N * g.OH * g.OW * CV;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
@@ -74,8 +41,8 @@ __global__ void __launch_bounds__(256) dw_fwd_kernel(const T* __restrict__ x, co
         const int ix = ox * g.sx + s * g.dx + g.px;
         if ((unsigned)ix >= (unsigned)g.W) continue;
         float xv[V], wv[V];
-        DV<T>::ld(x + ((int64_t)(n * g.H + iy) * g.W + ix) * g.ldx + c0, xv);
-        DV<T>::ld(w + (int64_t)(r * g.S + s) * g.ldw + c0, wv);
+        Vec16<T>::ld(x + ((int64_t)(n * g.H + iy) * g.W + ix) * g.ldx + c0, xv);
+        Vec16<T>::ld(w + (int64_t)(r * g.S + s) * g.ldw + c0, wv);
 #pragma unroll
         for (int e = 0; e < V; ++e) acc[e] = fmaf(xv[e], wv[e], acc[e]);
       }
@@ -84,8 +51,8 @@ __global__ void __launch_bounds__(256) dw_fwd_kernel(const T* __restrict__ x, co
     float r8[V];
 #pragma unroll
     for (int e = 0; e < V; ++e) r8[e] = 0.f;
-    if (res) DV<T>::ld(res + op * ldr + c0, r8);
-    if (aux) DV<T>::st(aux + op * g.ldy + c0, acc);
+    if (res) Vec16<T>::ld(res + op * ldr + c0, r8);
+    if (aux) Vec16<T>::st(aux + op * g.ldy + c0, acc);
     float o[V];
 #pragma unroll
     for (int e = 0; e < V; ++e) {
@@ -94,14 +61,14 @@ __global__ void __launch_bounds__(256) dw_fwd_kernel(const T* __restrict__ x, co
       if (shift) a += shift[c0 + e];
       o[e] = act_fwd(a + r8[e], act, slope);
     }
-    DV<T>::st(y + op * g.ldy + c0, o);
+    Vec16<T>::st(y + op * g.ldy + c0, o);
   }
 }
 
 template <typename T>
 __global__ void __launch_bounds__(256) dw_dgrad_kernel(const T* __restrict__ gy, const T* __restrict__ w,
                                                        T* __restrict__ gx, DG g) {
-  constexpr int V = DV<T>::V;
+  constexpr int V = Vec16<T>::V;
   const int CV = g.C / V;
   const int total = g.N * g.H * g.W * CV;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
@@ -124,13 +91,13 @@ __global__ void __launch_bounds__(256) dw_dgrad_kernel(const T* __restrict__ gy,
         const int ox = tx / g.sx;
         if (ox >= g.OW) continue;
         float gv[V], wv[V];
-        DV<T>::ld(gy + ((int64_t)(n * g.OH + oy) * g.OW + ox) * g.ldy + c0, gv);
-        DV<T>::ld(w + (int64_t)(r * g.S + s) * g.ldw + c0, wv);
+        Vec16<T>::ld(gy + ((int64_t)(n * g.OH + oy) * g.OW + ox) * g.ldy + c0, gv);
+        Vec16<T>::ld(w + (int64_t)(r * g.S + s) * g.ldw + c0, wv);
 #pragma unroll
         for (int e = 0; e < V; ++e) acc[e] = fmaf(gv[e], wv[e], acc[e]);
       }
     }
-    DV<T>::st(gx + ((int64_t)(n * g.H + iy) * g.W + ix) * g.ldx + c0, acc);
+    Vec16<T>::st(gx + ((int64_t)(n * g.H + iy) * g.W + ix) * g.ldx + c0, acc);
   }
 }
 
@@ -141,7 +108,7 @@ constexpr int WG_BLOCKS = 256;
 template <typename T>
 __global__ void __launch_bounds__(256) dw_wgrad_kernel(const T* __restrict__ x, const T* __restrict__ gy, DG g, int cpb,
                                                        float* __restrict__ part) {
-  constexpr int V = DV<T>::V;
+  constexpr int V = Vec16<T>::V;
   __shared__ float red[256][V + 1];
   const int CV = g.C / V;
   const int t = threadIdx.x;
@@ -162,8 +129,8 @@ __global__ void __launch_bounds__(256) dw_wgrad_kernel(const T* __restrict__ x, 
         const int iy = oy * g.sy + r * g.dy + g.py, ix = ox * g.sx + s * g.dx + g.px;
         if ((unsigned)iy >= (unsigned)g.H || (unsigned)ix >= (unsigned)g.W) continue;
         float xv[V], gv[V];
-        DV<T>::ld(x + ((int64_t)(n * g.H + iy) * g.W + ix) * g.ldx + c0, xv);
-        DV<T>::ld(gy + (int64_t)p * g.ldy + c0, gv);
+        Vec16<T>::ld(x + ((int64_t)(n * g.H + iy) * g.W + ix) * g.ldx + c0, xv);
+        Vec16<T>::ld(gy + (int64_t)p * g.ldy + c0, gv);
 #pragma unroll
         for (int e = 0; e < V; ++e) acc[e] = fmaf(xv[e], gv[e], acc[e]);
       }

@@ -22,25 +22,6 @@ __global__ void nchw_to_nhwc_kernel(const TI* x, TO* y, int64_t C, int64_t HW, i
 // one thread per pixel, 8 output channels per store (Cp % 8 == 0): the NCHW planes are read coalesced across
 // threads (consecutive pixels), the NHWC row written in 16-byte (bf16 / fp16) or 2 x 16-byte (fp32) stores,
 // one 64-bit index division per pixel instead of three per element
-template <typename TO> struct St8;
-template <> struct St8<bf16_t> {
-  __device__ __forceinline__ static void st(bf16_t* p, const float (&v)[8]) {
-    unsigned w[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w[i] = (unsigned)f32_to_bf16(v[2 * i]) | ((unsigned)f32_to_bf16(v[2 * i + 1]) << 16);
-    *(uint4*)p = make_uint4(w[0], w[1], w[2], w[3]);
-  }
-};
-template <> struct St8<f16_t> {
-  __device__ __forceinline__ static void st(f16_t* p, const float (&v)[8]) { H16::st8(p, v); }
-};
-template <> struct St8<float> {
-  __device__ __forceinline__ static void st(float* p, const float (&v)[8]) {
-    *(float4*)p = make_float4(v[0], v[1], v[2], v[3]);
-    *(float4*)(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
-  }
-};
-
 template <typename TI, typename TO>
 __global__ void nchw_to_nhwc_pix_kernel(const TI* __restrict__ x, TO* __restrict__ y, int64_t C, int64_t HW,
                                         int64_t Cp, int64_t P) {
@@ -51,7 +32,7 @@ __global__ void nchw_to_nhwc_pix_kernel(const TI* __restrict__ x, TO* __restrict
       float v[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = c0 + e < C ? io<TI>::ld(src, (c0 + e) * HW) : 0.f;
-      St8<TO>::st(y + pix * Cp + c0, v);
+      Vec<TO, 8>::st(y + pix * Cp + c0, v);
     }
   }
 }

@@ -12,10 +12,6 @@
 
 namespace {
 
-struct Strides {
-  int64_t n, c, h, w;
-};
-
 struct Axis {
   int in, out;
   float scale;
@@ -53,7 +49,7 @@ static Axis make_axis(int64_t in, int64_t out, bool align) {
 // I: index type of the element decode (int when N*C*Ho*Wo < 2^31: 64-bit divisions cost ~10x the 32-bit ones)
 template <typename T, typename I>
 __global__ void bilinear_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t N_, int64_t C_, Axis ah, Axis aw,
-                                    Strides xs, Strides ys, int c_fastest) {
+                                    Strides4 xs, Strides4 ys, int c_fastest) {
   const I N = (I)N_, C = (I)C_, Ho = ah.out, Wo = aw.out, total = N * C * Ho * Wo;
   for (I i = (I)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (I)gridDim.x * blockDim.x) {
     I n, c, oh, ow;
@@ -81,8 +77,8 @@ __global__ void bilinear_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, 
 // weights are computed once per pixel and each input pixel's channels come from one sector.  Per channel the
 // arithmetic is the generic kernel's (same roundings, same order): bit-identical results.
 template <typename T, int C>
-__global__ void bilinear_fwd_pix_kernel(const T* __restrict__ x, T* __restrict__ y, Axis ah, Axis aw, Strides xs,
-                                        Strides ys) {
+__global__ void bilinear_fwd_pix_kernel(const T* __restrict__ x, T* __restrict__ y, Axis ah, Axis aw, Strides4 xs,
+                                        Strides4 ys) {
   const int ow = blockIdx.x * blockDim.x + threadIdx.x, oh = blockIdx.y, n = blockIdx.z;
   if (ow >= aw.out) return;
   int h0, h1, w0, w1;
@@ -131,7 +127,7 @@ __device__ __forceinline__ void out_window(const Axis& a, int i, int& lo, int& h
 
 template <typename T, typename I>
 __global__ void bilinear_bwd_kernel(const T* __restrict__ gy, T* __restrict__ gx, int64_t N_, int64_t C_, Axis ah,
-                                    Axis aw, Strides gys, Strides gxs, int c_fastest) {
+                                    Axis aw, Strides4 gys, Strides4 gxs, int c_fastest) {
   const I N = (I)N_, C = (I)C_, H = ah.in, W = aw.in, total = N * C * H * W;
   for (I i = (I)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (I)gridDim.x * blockDim.x) {
     I n, c, h, w;
@@ -168,8 +164,8 @@ __global__ void bilinear_bwd_kernel(const T* __restrict__ gy, T* __restrict__ gx
 // backward of bilinear_fwd_pix_kernel: one thread per input pixel and all C <= 4 channels (the output window and
 // its weights computed once per pixel); per channel the generic kernel's gather in the same order: bit-identical
 template <typename T, int C>
-__global__ void bilinear_bwd_pix_kernel(const T* __restrict__ gy, T* __restrict__ gx, Axis ah, Axis aw, Strides gys,
-                                        Strides gxs) {
+__global__ void bilinear_bwd_pix_kernel(const T* __restrict__ gy, T* __restrict__ gx, Axis ah, Axis aw, Strides4 gys,
+                                        Strides4 gxs) {
   const int w = blockIdx.x * blockDim.x + threadIdx.x, h = blockIdx.y, n = blockIdx.z;
   if (w >= aw.in) return;
   int ohlo, ohhi, owlo, owhi;
@@ -211,6 +207,8 @@ __global__ void bilinear_bwd_pix_kernel(const T* __restrict__ gy, T* __restrict_
 // thread per (pixel, 8-channel chunk), blockIdx.y = output row, blockIdx.z = image -- no per-element index decode,
 // 16-byte loads and stores.  Per channel the arithmetic is the generic kernels' (same roundings, same order), so
 // the results are bit-identical to them.
+
+// (local, not Chunk<T, 8>::pack: its pairwise conversion changes the fp16 kernels' register allocation)
 template <typename T>
 __device__ __forceinline__ uint4 pack8(const float (&v)[8]) {
   T o[8];
@@ -221,7 +219,7 @@ __device__ __forceinline__ uint4 pack8(const float (&v)[8]) {
 
 template <typename T>
 __global__ void __launch_bounds__(256) bilinear_fwd_nhwc_kernel(const T* __restrict__ x, T* __restrict__ y, int C8,
-                                                                Axis ah, Axis aw, Strides xs, Strides ys) {
+                                                                Axis ah, Axis aw, Strides4 xs, Strides4 ys) {
   const int oh = blockIdx.y, n = blockIdx.z;
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= aw.out * C8) return;
@@ -251,7 +249,7 @@ __global__ void __launch_bounds__(256) bilinear_fwd_nhwc_kernel(const T* __restr
 
 template <typename T>
 __global__ void __launch_bounds__(256) bilinear_bwd_nhwc_kernel(const T* __restrict__ gy, T* __restrict__ gx, int C8,
-                                                                Axis ah, Axis aw, Strides gys, Strides gxs) {
+                                                                Axis ah, Axis aw, Strides4 gys, Strides4 gxs) {
   const int h = blockIdx.y, n = blockIdx.z;
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= aw.in * C8) return;
@@ -298,7 +296,7 @@ __global__ void __launch_bounds__(256) bilinear_bwd_nhwc_kernel(const T* __restr
 // walks one axis (<= 2^k + 1 loads) over a grid of N x Ho x w (resp. N x h x w) chunks.
 template <typename T>
 __global__ void __launch_bounds__(256) bilinear_bwd_rows_nhwc_kernel(const T* __restrict__ gy, float* __restrict__ rs,
-                                                                     int C8, int Ho, Axis aw, Strides gys) {
+                                                                     int C8, int Ho, Axis aw, Strides4 gys) {
   const int oh = blockIdx.y, n = blockIdx.z;
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= aw.in * C8) return;
@@ -328,7 +326,7 @@ __global__ void __launch_bounds__(256) bilinear_bwd_rows_nhwc_kernel(const T* __
 
 template <typename T>
 __global__ void __launch_bounds__(256) bilinear_bwd_cols_nhwc_kernel(const float* __restrict__ rs, T* __restrict__ gx,
-                                                                     int C8, int Ho, Axis ah, int Wi, Strides gxs) {
+                                                                     int C8, int Ho, Axis ah, int Wi, Strides4 gxs) {
   const int h = blockIdx.y, n = blockIdx.z;
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= Wi * C8) return;
@@ -354,8 +352,8 @@ __global__ void __launch_bounds__(256) bilinear_bwd_cols_nhwc_kernel(const float
 }
 
 // the NHWC kernels apply: 16-bit, channels fastest in both tensors, 16-byte aligned chunks, grid dims in range
-static bool nhwc_ok(const void* a, const void* b, int64_t N, int64_t C, int64_t rows, int64_t cols, const Strides& as,
-                    const Strides& bs, int dt) {
+static bool nhwc_ok(const void* a, const void* b, int64_t N, int64_t C, int64_t rows, int64_t cols, const Strides4& as,
+                    const Strides4& bs, int dt) {
   if (dt != SSSEG_BF16 && dt != SSSEG_F16) return false;
   if (as.c != 1 || bs.c != 1 || C % 8 || C < 8) return false;
   if (((uintptr_t)a | (uintptr_t)b) % 16) return false;
@@ -363,7 +361,6 @@ static bool nhwc_ok(const void* a, const void* b, int64_t N, int64_t C, int64_t 
   return N <= 65535 && rows <= 65535 && cols * (C / 8) < 0x7fffffffLL;
 }
 
-static Strides to_strides(const int64_t* s) { return Strides{s[0], s[1], s[2], s[3]}; }
 
 // the per-pixel fp32 kernels apply: C <= 4 channels, grid dims in range (SSSEG_BIL_PIX=0 turns them off for A/B)
 static bool pix_ok(int64_t N, int64_t C, int64_t rows, int64_t cols, int dt) {
@@ -383,7 +380,7 @@ extern "C" int ssseg_bilinear_fwd(const void* x, void* y, int64_t N, int64_t C, 
   const int64_t total = N * C * Ho * Wo;
   if (total == 0) return 0;
   const Axis ah = make_axis(H, Ho, align_corners), aw = make_axis(W, Wo, align_corners);
-  const Strides xs = to_strides(xs4), ys = to_strides(ys4);
+  const Strides4 xs = strides4(xs4), ys = strides4(ys4);
   const int cf = ys.c == 1 && C > 1;
   hipStream_t s = (hipStream_t)stream;
   if (nhwc_ok(x, y, N, C, Ho, Wo, xs, ys, dt)) {
@@ -435,7 +432,7 @@ extern "C" int ssseg_bilinear_bwd_ws(const void* gy, void* gx, int64_t N, int64_
                                      void* ws, size_t ws_bytes, ssseg_stream_t stream) {
   if (!gy || !gx || !gys4 || !gxs4 || N < 0 || C < 0 || H < 1 || W < 1 || Ho < 1 || Wo < 1) return SSSEG_EINVAL;
   if (N * C * H * W == 0) return 0;
-  const Strides gys = to_strides(gys4), gxs = to_strides(gxs4);
+  const Strides4 gys = strides4(gys4), gxs = strides4(gxs4);
   if (!ws || !nhwc_ok(gy, gx, N, C, H, W, gys, gxs, dt) || !nhwc_ok(gy, gx, N, C, Ho, W, gys, gxs, dt))
     return ssseg_bilinear_bwd(gy, gx, N, C, H, W, Ho, Wo, gys4, gxs4, align_corners, dt, stream);
   if (ws_bytes < ssseg_bilinear_bwd_workspace_bytes(N, C, W, Ho) || ((uintptr_t)ws & 15)) return SSSEG_EWORKSPACE;
@@ -466,7 +463,7 @@ extern "C" int ssseg_bilinear_bwd(const void* gy, void* gx, int64_t N, int64_t C
   const int64_t total = N * C * H * W;
   if (total == 0) return 0;
   const Axis ah = make_axis(H, Ho, align_corners), aw = make_axis(W, Wo, align_corners);
-  const Strides gys = to_strides(gys4), gxs = to_strides(gxs4);
+  const Strides4 gys = strides4(gys4), gxs = strides4(gxs4);
   const int cf = gxs.c == 1 && C > 1;
   hipStream_t s = (hipStream_t)stream;
   if (nhwc_ok(gy, gx, N, C, H, W, gys, gxs, dt)) {

@@ -67,39 +67,6 @@ __global__ void maxpool_bwd_kernel(const T* __restrict__ gy, const uint8_t* __re
 
 // 16-byte channel-chunk variants (C % (16/sizeof(T)) == 0, < 2^31 chunks): one thread per (pixel, chunk),
 // 32-bit index math, the window's taps loaded as 16-byte vectors, argmax bytes stored 8/4 at a time.
-template <typename T> struct VC;
-template <> struct VC<bf16_t> {
-  static constexpr int V = 8;
-  __device__ __forceinline__ static void ld(const bf16_t* p, float (&v)[8]) {
-    const uint4 q = *(const uint4*)p;
-    const unsigned w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      v[2 * i] = __uint_as_float(w[i] << 16);
-      v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
-  }
-  __device__ __forceinline__ static void st(bf16_t* p, const float (&v)[8]) {
-    unsigned w[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w[i] = (unsigned)f32_to_bf16(v[2 * i]) | ((unsigned)f32_to_bf16(v[2 * i + 1]) << 16);
-    *(uint4*)p = make_uint4(w[0], w[1], w[2], w[3]);
-  }
-};
-template <> struct VC<f16_t> {
-  static constexpr int V = 8;
-  __device__ __forceinline__ static void ld(const f16_t* p, float (&v)[8]) { H16::ld8(p, v); }
-  __device__ __forceinline__ static void st(f16_t* p, const float (&v)[8]) { H16::st8(p, v); }
-};
-template <> struct VC<float> {
-  static constexpr int V = 4;
-  __device__ __forceinline__ static void ld(const float* p, float (&v)[4]) {
-    const float4 q = *(const float4*)p;
-    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-  }
-  __device__ __forceinline__ static void st(float* p, const float (&v)[4]) { *(float4*)p = make_float4(v[0], v[1], v[2], v[3]); }
-};
-
 template <int V> struct IdxVec;
 template <> struct IdxVec<8> {
   __device__ __forceinline__ static void st(uint8_t* p, const int (&b)[8]) {
@@ -137,7 +104,7 @@ template <> struct IdxVec<4> {
 template <typename T>
 __global__ void maxpool_fwd_vec_kernel(const T* __restrict__ x, T* __restrict__ y, uint8_t* __restrict__ idx, int N,
                                        int H, int W, int C, int OH, int OW, int k, int s, int p) {
-  constexpr int V = VC<T>::V;
+  constexpr int V = Vec16<T>::V;
   const int CV = C / V;
   const int total = N * OH * OW * CV;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
@@ -180,7 +147,7 @@ __global__ void maxpool_fwd_vec_kernel(const T* __restrict__ x, T* __restrict__ 
         }
       }
       const int64_t o = (int64_t)i * V;
-      VC<T>::st(y + o, m);
+      Vec16<T>::st(y + o, m);
       IdxVec<V>::st(idx + o, best);
       continue;
     }
@@ -191,7 +158,7 @@ __global__ void maxpool_fwd_vec_kernel(const T* __restrict__ x, T* __restrict__ 
         const int iw = ow * s - p + kw;
         if (iw < 0 || iw >= W) continue;
         float v[V];
-        VC<T>::ld(x + ((int64_t)(n * H + ih) * W + iw) * C + cv * V, v);
+        Vec16<T>::ld(x + ((int64_t)(n * H + ih) * W + iw) * C + cv * V, v);
         const int tap = kh * k + kw;
 #pragma unroll
         for (int e = 0; e < V; ++e) {   // PyTorch order: first valid tap, then v > max or NaN
@@ -204,7 +171,7 @@ __global__ void maxpool_fwd_vec_kernel(const T* __restrict__ x, T* __restrict__ 
       }
     }
     const int64_t o = (int64_t)i * V;
-    VC<T>::st(y + o, m);
+    Vec16<T>::st(y + o, m);
     IdxVec<V>::st(idx + o, best);
   }
 }
@@ -213,7 +180,7 @@ template <typename T>
 __global__ void maxpool_bwd_vec_kernel(const T* __restrict__ gy, const uint8_t* __restrict__ idx,
                                        const T* __restrict__ res, T* __restrict__ gx, int N, int H, int W, int C,
                                        int OH, int OW, int k, int s, int p) {
-  constexpr int V = VC<T>::V;
+  constexpr int V = Vec16<T>::V;
   const int CV = C / V;
   const int total = N * H * W * CV;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
@@ -226,7 +193,7 @@ __global__ void maxpool_bwd_vec_kernel(const T* __restrict__ gy, const uint8_t* 
     const int ow0 = max(0, (iw + p - k + s) / s), ow1 = min(OW - 1, (iw + p) / s);
     float acc[V];
     if (res)
-      VC<T>::ld(res + (int64_t)i * V, acc);   // the parked gradient of x (GradJoin), added in the same pass
+      Vec16<T>::ld(res + (int64_t)i * V, acc);   // the parked gradient of x (GradJoin), added in the same pass
     else
 #pragma unroll
       for (int e = 0; e < V; ++e) acc[e] = 0.f;
@@ -258,7 +225,7 @@ __global__ void maxpool_bwd_vec_kernel(const T* __restrict__ gy, const uint8_t* 
           acc[e] += b == tap[c] ? g[e] : 0.f;
         }
       }
-      VC<T>::st(gx + (int64_t)i * V, acc);
+      Vec16<T>::st(gx + (int64_t)i * V, acc);
       continue;
     }
     for (int oh = oh0; oh <= oh1; ++oh) {
@@ -271,13 +238,13 @@ __global__ void maxpool_bwd_vec_kernel(const T* __restrict__ gy, const uint8_t* 
         int b[V];
         IdxVec<V>::ld(idx + o, b);
         float g[V];
-        VC<T>::ld(gy + o, g);
+        Vec16<T>::ld(gy + o, g);
         const int tap = kh * k + kw;
 #pragma unroll
         for (int e = 0; e < V; ++e) acc[e] += b[e] == tap ? g[e] : 0.f;
       }
     }
-    VC<T>::st(gx + (int64_t)i * V, acc);
+    Vec16<T>::st(gx + (int64_t)i * V, acc);
   }
 }
 

@@ -9,6 +9,7 @@
 // The random inputs (a 31-bit key per image and class, four uniforms per image) come from Philox on CowMix's per-device
 // seed and counter (ssseg_mixmask_draw_dev), so a captured step replays fresh masks.
 #include "common.h"
+#include "philox.h"
 
 namespace {
 
@@ -161,28 +162,6 @@ __global__ void __launch_bounds__(MM_TILE) cutmix_mask_kernel(const float* __res
   }
 }
 
-__device__ __forceinline__ void philox_round(unsigned (&c)[4], unsigned k0, unsigned k1) {
-  const unsigned M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
-  unsigned hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0];
-  unsigned hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
-  unsigned n0 = hi1 ^ c[1] ^ k0, n1 = lo1, n2 = hi0 ^ c[3] ^ k1, n3 = lo0;
-  c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
-
-__device__ __forceinline__ void philox(unsigned (&c)[4], uint64_t ctr, unsigned stream_id, uint64_t seed) {
-  c[0] = (unsigned)ctr;
-  c[1] = (unsigned)(ctr >> 32);
-  c[2] = stream_id;
-  c[3] = 0u;
-  unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    philox_round(c, k0, k1);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
-
 // Streams 3 and 4 of the key (0: CowMix noise, 1: CowMix p / sigma, 2: the affine views).  Item i < B*Q (Q = ceil(C/4))
 // is the Philox block at counter offset + i of stream 3: four 31-bit keys of image i / Q, classes 4 (i % Q) ...;
 // item B*Q + b is the block at counter offset + B*Q + b of stream 4: the four 24-bit uniforms of image b.
@@ -195,17 +174,19 @@ __global__ void __launch_bounds__(256) mixmask_draw_kernel(int* __restrict__ key
     if (i < B * Q ? !keys : !params) continue;   // an output that is not asked for keeps its counters
     unsigned c[4];
     if (i < B * Q) {
-      philox(c, offset + (uint64_t)i, 3u, seed);
+      philox_block(c, offset + (uint64_t)i, 3u);
+      philox4x32_10(c, seed);
       const int64_t b = i / Q;
       const int c0 = 4 * (int)(i - b * Q);
 #pragma unroll
       for (int j = 0; j < 4; ++j)
         if (c0 + j < C) keys[b * C + c0 + j] = (int)(c[j] & 0x7fffffffu);
     } else {
-      philox(c, offset + (uint64_t)i, 4u, seed);
+      philox_block(c, offset + (uint64_t)i, 4u);
+      philox4x32_10(c, seed);
       const int64_t b = i - B * Q;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) params[4 * b + j] = (float)(c[j] >> 8) * (1.0f / 16777216.0f);
+      for (int j = 0; j < 4; ++j) params[4 * b + j] = philox_u01(c[j]);
     }
   }
 }

@@ -149,18 +149,11 @@ __device__ __forceinline__ void update(const StepArgs& h, const StepScalars& c, 
   }
 }
 
-__device__ __forceinline__ float4 ld4(const float* x, int64_t i) { return ((const float4*)x)[i]; }
-__device__ __forceinline__ void st4(float* x, int64_t i, const float (&a)[4]) {
-  ((float4*)x)[i] = make_float4(a[0], a[1], a[2], a[3]);
-}
-__device__ __forceinline__ void unpack(const float4& q, float (&a)[4]) {
-  a[0] = q.x; a[1] = q.y; a[2] = q.z; a[3] = q.w;
-}
-
 template <int MODE, int VER>
 __global__ void __launch_bounds__(256) optim_step_kernel(StepArgs h) {
   constexpr bool HAS_S = MODE == SSSEG_OPT_ADAMOD || MODE == SSSEG_OPT_DIFFMOD;
   constexpr bool HAS_PREV = MODE == SSSEG_OPT_DIFFGRAD || MODE == SSSEG_OPT_DIFFMOD;
+  using F4 = Chunk<float, 4>;   // every array is walked in 16-byte pieces, indexed as float4 (h.n4 of them)
   if (h.st[ST_SKIP] != 0.0) return;
   StepScalars c;
   c.coef = (float)h.st[ST_COEF];
@@ -175,21 +168,21 @@ __global__ void __launch_bounds__(256) optim_step_kernel(StepArgs h) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < h.n4; i += (int64_t)gridDim.x * blockDim.x) {
     float p[4], g[4], m[4], v[4], s[4] = {0.f, 0.f, 0.f, 0.f}, prev[4] = {0.f, 0.f, 0.f, 0.f},
                                   slow[4] = {0.f, 0.f, 0.f, 0.f};
-    unpack(ld4(h.p, i), p);
-    unpack(ld4(h.g, i), g);
-    unpack(ld4(h.m, i), m);
-    unpack(ld4(h.v, i), v);
-    if (HAS_S) unpack(ld4(h.s, i), s);
-    if (HAS_PREV) unpack(ld4(h.prev, i), prev);
-    if (slow_ld) unpack(ld4(h.slow, i), slow);
+    F4::cvt(((const float4*)h.p)[i], p);
+    F4::cvt(((const float4*)h.g)[i], g);
+    F4::cvt(((const float4*)h.m)[i], m);
+    F4::cvt(((const float4*)h.v)[i], v);
+    if (HAS_S) F4::cvt(((const float4*)h.s)[i], s);
+    if (HAS_PREV) F4::cvt(((const float4*)h.prev)[i], prev);
+    if (slow_ld) F4::cvt(((const float4*)h.slow)[i], slow);
 #pragma unroll
     for (int j = 0; j < 4; ++j) update<MODE, VER>(h, c, p[j], g[j], m[j], v[j], s[j], prev[j], slow[j]);
-    st4(h.p, i, p);
-    st4(h.m, i, m);
-    st4(h.v, i, v);
-    if (HAS_S) st4(h.s, i, s);
-    if (HAS_PREV) st4(h.prev, i, prev);
-    if (slow_st) st4(h.slow, i, slow);
+    ((float4*)h.p)[i] = F4::pack(p);
+    ((float4*)h.m)[i] = F4::pack(m);
+    ((float4*)h.v)[i] = F4::pack(v);
+    if (HAS_S) ((float4*)h.s)[i] = F4::pack(s);
+    if (HAS_PREV) ((float4*)h.prev)[i] = F4::pack(prev);
+    if (slow_st) ((float4*)h.slow)[i] = F4::pack(slow);
   }
 }
 

@@ -84,34 +84,16 @@ __device__ __forceinline__ void ps_elem(float& p, float& g, float& b, float& e, 
   if (EMA) e = fmaf(p, h.beta, __fmul_rn(e, h.a));
 }
 
-// V consecutive elements at arena index i (V = 4: one 16-byte piece per array)
-template <int V> struct PsVec;
-template <> struct PsVec<4> {
-  typedef float4 raw;
-  __device__ __forceinline__ static raw ld(const float* p, long long i) { return *(const float4*)(p + i); }
-  __device__ __forceinline__ static void st(float* p, long long i, const float (&v)[4]) {
-    *(float4*)(p + i) = make_float4(v[0], v[1], v[2], v[3]);
-  }
-  __device__ __forceinline__ static void get(const raw& q, float (&v)[4]) {
-    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-  }
-};
-template <> struct PsVec<1> {
-  typedef float raw;
-  __device__ __forceinline__ static raw ld(const float* p, long long i) { return p[i]; }
-  __device__ __forceinline__ static void st(float* p, long long i, const float (&v)[1]) { p[i] = v[0]; }
-  __device__ __forceinline__ static void get(const raw& q, float (&v)[1]) { v[0] = q; }
-};
-
 // phase 1 of a conv tile: rows a0 .. a0 + na of the source, L elements each from column b0, in source order; the
 // updated values go back to the arenas and, as bf16, into the LDS images [al][bl][t] (row stride RSP)
 template <bool SGD, bool MOM, bool EMA, int V>
 __device__ __forceinline__ void ps_conv_update(const PsArgs& h, const PsCoef& k, long long base, int rowlen, int na,
                                                int L, int TB, int RS, int RSP, bf16_t* sS, bf16_t* sT) {
+  using CK = Chunk<float, V>;
   const int Lq = L / V, nq = na * Lq;
   const float iLq = 1.f / (float)Lq, iRS = 1.f / (float)RS;
   for (int u0 = 0; u0 < nq; u0 += 256 * PS_U) {
-    typename PsVec<V>::raw P[PS_U], G[PS_U], Bf[PS_U], Em[PS_U];
+    typename CK::raw P[PS_U], G[PS_U], Bf[PS_U], Em[PS_U];
     int gi[PS_U], li[PS_U], tt[PS_U];   // (a weight has < 2^31 elements: 32-bit offsets from its tile's base)
     // every load of the batch first, from clamped addresses: no branch around a load
 #pragma unroll
@@ -123,32 +105,32 @@ __device__ __forceinline__ void ps_conv_update(const PsArgs& h, const PsCoef& k,
       tt[it] = r - bl * RS;
       li[it] = (al * TB + bl) * RSP + tt[it];
       gi[it] = al * rowlen + r;
-      P[it] = PsVec<V>::ld(h.p + base, gi[it]);
-      if (SGD) G[it] = PsVec<V>::ld(h.g + base, gi[it]);
-      if (MOM) Bf[it] = PsVec<V>::ld(h.buf + base, gi[it]);
-      if (EMA) Em[it] = PsVec<V>::ld(h.ema + base, gi[it]);
+      P[it] = CK::ld(h.p + base + gi[it]);
+      if (SGD) G[it] = CK::ld(h.g + base + gi[it]);
+      if (MOM) Bf[it] = CK::ld(h.buf + base + gi[it]);
+      if (EMA) Em[it] = CK::ld(h.ema + base + gi[it]);
     }
 #pragma unroll
     for (int it = 0; it < PS_U; ++it) {
       if (u0 + it * 256 + (int)threadIdx.x >= nq) continue;
       float p[V], g[V], b[V], e[V];
-      PsVec<V>::get(P[it], p);
-      if (SGD) PsVec<V>::get(G[it], g);
-      if (MOM) PsVec<V>::get(Bf[it], b);
-      if (EMA) PsVec<V>::get(Em[it], e);
+      CK::cvt(P[it], p);
+      if (SGD) CK::cvt(G[it], g);
+      if (MOM) CK::cvt(Bf[it], b);
+      if (EMA) CK::cvt(Em[it], e);
 #pragma unroll
       for (int x = 0; x < V; ++x) ps_elem<SGD, MOM, EMA>(p[x], g[x], b[x], e[x], h, k);
       if (SGD && !k.skip) {
-        PsVec<V>::st(h.p + base, gi[it], p);
-        if (MOM) PsVec<V>::st(h.buf + base, gi[it], b);
+        Vec<float, V>::st(h.p + base + gi[it], p);
+        if (MOM) Vec<float, V>::st(h.buf + base + gi[it], b);
       }
-      if (EMA) PsVec<V>::st(h.ema + base, gi[it], e);
+      if (EMA) Vec<float, V>::st(h.ema + base + gi[it], e);
       if (h.clear) {
 #pragma unroll
         for (int x = 0; x < V; ++x) g[x] = 0.f;
-        PsVec<V>::st(h.g + base, gi[it], g);
+        Vec<float, V>::st(h.g + base + gi[it], g);
       } else if (SGD && !k.skip) {
-        PsVec<V>::st(h.g + base, gi[it], g);   // left clipped, as sgd_kernel leaves it
+        Vec<float, V>::st(h.g + base + gi[it], g);   // left clipped, as sgd_kernel leaves it
       }
       int o = li[it], t = tt[it];
 #pragma unroll
@@ -211,37 +193,38 @@ __device__ __forceinline__ void ps_flat(const PsArgs& h, const PsCoef& k, long l
   const long long lo = off, hi = off + n;
   const long long first = (off >> 2) * 4 + (long long)tile * PS_FLAT;
   const long long last = ((hi - 1) >> 2) * 4;   // the last piece of the range
-  float4 P[PS_U], G[PS_U], Bf[PS_U], Em[PS_U];
+  using F4 = Chunk<float, 4>;
+  F4::raw P[PS_U], G[PS_U], Bf[PS_U], Em[PS_U];
   long long gi[PS_U];
 #pragma unroll
   for (int it = 0; it < PS_U; ++it) {
     gi[it] = first + (long long)(it * 256 + (int)threadIdx.x) * 4;
     const long long i = gi[it] < last ? gi[it] : last;
-    P[it] = *(const float4*)(h.p + i);
-    if (SGD) G[it] = *(const float4*)(h.g + i);
-    if (MOM) Bf[it] = *(const float4*)(h.buf + i);
-    if (EMA) Em[it] = *(const float4*)(h.ema + i);
+    P[it] = F4::ld(h.p + i);
+    if (SGD) G[it] = F4::ld(h.g + i);
+    if (MOM) Bf[it] = F4::ld(h.buf + i);
+    if (EMA) Em[it] = F4::ld(h.ema + i);
   }
 #pragma unroll
   for (int it = 0; it < PS_U; ++it) {
     const long long i = gi[it];
     if (i > last) continue;
     float p[4], g[4], b[4], e[4];
-    PsVec<4>::get(P[it], p);
-    if (SGD) PsVec<4>::get(G[it], g);
-    if (MOM) PsVec<4>::get(Bf[it], b);
-    if (EMA) PsVec<4>::get(Em[it], e);
+    F4::cvt(P[it], p);
+    if (SGD) F4::cvt(G[it], g);
+    if (MOM) F4::cvt(Bf[it], b);
+    if (EMA) F4::cvt(Em[it], e);
 #pragma unroll
     for (int x = 0; x < 4; ++x) ps_elem<SGD, MOM, EMA>(p[x], g[x], b[x], e[x], h, k);
     const bool wr = SGD && !k.skip;
     if (i >= lo && i + 4 <= hi) {
       if (wr) {
-        PsVec<4>::st(h.p, i, p);
-        if (MOM) PsVec<4>::st(h.buf, i, b);
+        Vec<float, 4>::st(h.p + i, p);
+        if (MOM) Vec<float, 4>::st(h.buf + i, b);
       }
-      if (EMA) PsVec<4>::st(h.ema, i, e);
+      if (EMA) Vec<float, 4>::st(h.ema + i, e);
       if (h.clear) *(float4*)(h.g + i) = make_float4(0.f, 0.f, 0.f, 0.f);
-      else if (wr) PsVec<4>::st(h.g, i, g);
+      else if (wr) Vec<float, 4>::st(h.g + i, g);
     } else {
 #pragma unroll
       for (int x = 0; x < 4; ++x) {

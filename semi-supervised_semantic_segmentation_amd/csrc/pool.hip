@@ -8,41 +8,9 @@
 // NHWC activations are processed in 16-byte channel chunks (8 bf16 / 4 f32; the physical channel count is a
 // multiple of the chunk), so every activation load and store is a full dwordx4.
 #include "common.h"
+#include "philox.h"
 
 namespace {
-
-template <typename T> struct CV16;
-template <> struct CV16<bf16_t> {
-  static constexpr int V = 8;
-  __device__ __forceinline__ static void ld(const bf16_t* p, float (&v)[8]) {
-    const uint4 q = *(const uint4*)p;
-    const unsigned w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      v[2 * i] = __uint_as_float(w[i] << 16);
-      v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
-  }
-  __device__ __forceinline__ static void st(bf16_t* p, const float (&v)[8]) {
-    unsigned w[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w[i] = (unsigned)f32_to_bf16(v[2 * i]) | ((unsigned)f32_to_bf16(v[2 * i + 1]) << 16);
-    *(uint4*)p = make_uint4(w[0], w[1], w[2], w[3]);
-  }
-};
-template <> struct CV16<f16_t> {
-  static constexpr int V = 8;
-  __device__ __forceinline__ static void ld(const f16_t* p, float (&v)[8]) { H16::ld8(p, v); }
-  __device__ __forceinline__ static void st(f16_t* p, const float (&v)[8]) { H16::st8(p, v); }
-};
-template <> struct CV16<float> {
-  static constexpr int V = 4;
-  __device__ __forceinline__ static void ld(const float* p, float (&v)[4]) {
-    const float4 q = *(const float4*)p;
-    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-  }
-  __device__ __forceinline__ static void st(float* p, const float (&v)[4]) { *(float4*)p = make_float4(v[0], v[1], v[2], v[3]); }
-};
 
 // ---- AvgPool2d(k, s, p), ceil_mode False, count_include_pad True (PyTorch's defaults) --------------------
 // divisor = window clipped to the padded map [-p, H+p) (PyTorch avg_pool2d); taps summed in (kh, kw) order
@@ -50,7 +18,7 @@ template <> struct CV16<float> {
 template <typename T>
 __global__ void avgpool_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, int N, int H, int W, int C, int OH,
                                    int OW, int k, int s, int p) {
-  constexpr int V = CV16<T>::V;
+  constexpr int V = Vec16<T>::V;
   const int CV = C / V;
   const int total = N * OH * OW * CV;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
@@ -72,13 +40,13 @@ __global__ void avgpool_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, i
     for (int ih = hs; ih < he; ++ih)
       for (int iw = ws; iw < we; ++iw) {
         float v[V];
-        CV16<T>::ld(x + ((int64_t)(n * H + ih) * W + iw) * C + cv * V, v);
+        Vec16<T>::ld(x + ((int64_t)(n * H + ih) * W + iw) * C + cv * V, v);
 #pragma unroll
         for (int e = 0; e < V; ++e) acc[e] += v[e];
       }
 #pragma unroll
     for (int e = 0; e < V; ++e) acc[e] = acc[e] / div;
-    CV16<T>::st(y + (int64_t)i * V, acc);
+    Vec16<T>::st(y + (int64_t)i * V, acc);
   }
 }
 
@@ -86,7 +54,7 @@ __global__ void avgpool_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, i
 template <typename T>
 __global__ void avgpool_bwd_kernel(const T* __restrict__ gy, T* __restrict__ gx, int N, int H, int W, int C, int OH,
                                    int OW, int k, int s, int p) {
-  constexpr int V = CV16<T>::V;
+  constexpr int V = Vec16<T>::V;
   const int CV = C / V;
   const int total = N * H * W * CV;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
@@ -109,12 +77,12 @@ __global__ void avgpool_bwd_kernel(const T* __restrict__ gy, T* __restrict__ gx,
         if (iw < ws || iw >= ws + k) continue;
         const float div = (float)(hdiv * (min(ws + k, W + p) - ws));
         float g[V];
-        CV16<T>::ld(gy + ((int64_t)(n * OH + oh) * OW + ow) * C + cv * V, g);
+        Vec16<T>::ld(gy + ((int64_t)(n * OH + oh) * OW + ow) * C + cv * V, g);
 #pragma unroll
         for (int e = 0; e < V; ++e) acc[e] += g[e] / div;
       }
     }
-    CV16<T>::st(gx + (int64_t)i * V, acc);
+    Vec16<T>::st(gx + (int64_t)i * V, acc);
   }
 }
 
@@ -126,7 +94,7 @@ constexpr int GAP_SPLITS_MAX = 64;
 template <typename T>
 __global__ void __launch_bounds__(256) gap_partial_kernel(const T* __restrict__ x, float* __restrict__ part, int HW,
                                                           int C, int splits) {
-  constexpr int V = CV16<T>::V;
+  constexpr int V = Vec16<T>::V;
   __shared__ float red[4][64][V];
   const int t = threadIdx.x, cl = t & 63, row = t >> 6;
   const int n = blockIdx.x, sp = blockIdx.z;
@@ -141,16 +109,16 @@ __global__ void __launch_bounds__(256) gap_partial_kernel(const T* __restrict__ 
     int pix = p0 + row;
     for (; pix + 12 < p1; pix += 16) {   // 4 independent loads in flight
       float a[V], b[V], c[V], d[V];
-      CV16<T>::ld(xb + (int64_t)pix * C, a);
-      CV16<T>::ld(xb + (int64_t)(pix + 4) * C, b);
-      CV16<T>::ld(xb + (int64_t)(pix + 8) * C, c);
-      CV16<T>::ld(xb + (int64_t)(pix + 12) * C, d);
+      Vec16<T>::ld(xb + (int64_t)pix * C, a);
+      Vec16<T>::ld(xb + (int64_t)(pix + 4) * C, b);
+      Vec16<T>::ld(xb + (int64_t)(pix + 8) * C, c);
+      Vec16<T>::ld(xb + (int64_t)(pix + 12) * C, d);
 #pragma unroll
       for (int e = 0; e < V; ++e) acc[e] += (a[e] + b[e]) + (c[e] + d[e]);
     }
     for (; pix < p1; pix += 4) {
       float a[V];
-      CV16<T>::ld(xb + (int64_t)pix * C, a);
+      Vec16<T>::ld(xb + (int64_t)pix * C, a);
 #pragma unroll
       for (int e = 0; e < V; ++e) acc[e] += a[e];
     }
@@ -179,17 +147,17 @@ __global__ void gap_final_kernel(const float* __restrict__ part, T* __restrict__
 template <typename T>
 __global__ void gap_bwd_kernel(const T* __restrict__ gy, T* __restrict__ gx, int N, int HW, int C, int64_t ldgy,
                                float inv_hw) {
-  constexpr int V = CV16<T>::V;
+  constexpr int V = Vec16<T>::V;
   const int CV = C / V;
   const int64_t total = (int64_t)N * HW * CV;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int cv = (int)(i % CV);
     const int n = (int)(i / ((int64_t)HW * CV));
     float g[V];
-    CV16<T>::ld(gy + (int64_t)n * ldgy + cv * V, g);
+    Vec16<T>::ld(gy + (int64_t)n * ldgy + cv * V, g);
 #pragma unroll
     for (int e = 0; e < V; ++e) g[e] *= inv_hw;
-    CV16<T>::st(gx + i * V, g);
+    Vec16<T>::st(gx + i * V, g);
   }
 }
 
@@ -200,50 +168,37 @@ struct Ptr8 {
 
 template <typename T>
 __global__ void add_n_kernel(Ptr8 xs, int n, T* __restrict__ y, int64_t nchunks, int act, float slope) {
-  constexpr int V = CV16<T>::V;
+  constexpr int V = Vec16<T>::V;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nchunks; i += (int64_t)gridDim.x * blockDim.x) {
     float acc[V];
-    CV16<T>::ld((const T*)xs.p[0] + i * V, acc);
+    Vec16<T>::ld((const T*)xs.p[0] + i * V, acc);
     for (int j = 1; j < n; ++j) {
       float v[V];
-      CV16<T>::ld((const T*)xs.p[j] + i * V, v);
+      Vec16<T>::ld((const T*)xs.p[j] + i * V, v);
 #pragma unroll
       for (int e = 0; e < V; ++e) acc[e] += v[e];
     }
 #pragma unroll
     for (int e = 0; e < V; ++e) acc[e] = act_fwd(acc[e], act, slope);
-    CV16<T>::st(y + i * V, acc);
+    Vec16<T>::st(y + i * V, acc);
   }
 }
 
 // ---- Dropout: keep with probability 1-p, kept values scaled by 1/(1-p) -----------------------------------------
 // Counter-based (Philox-4x32-10, counter = offset + i/4, key = seed): the backward regenerates the same mask
 // from (seed, offset), so no mask is stored.
-__device__ __forceinline__ void philox4(unsigned (&c)[4], uint64_t seed) {
-  unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
-    const unsigned hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0];
-    const unsigned hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
-    const unsigned n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-    c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
-
 template <typename T>
 __global__ void dropout_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t n4, float p, float scale,
                                uint64_t seed, uint64_t offset, const unsigned long long* __restrict__ offset_dev) {
   if (offset_dev) offset = (uint64_t)*offset_dev;
   for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n4; q += (int64_t)gridDim.x * blockDim.x) {
     const uint64_t ctr = offset + (uint64_t)q;
-    unsigned c[4] = {(unsigned)ctr, (unsigned)(ctr >> 32), 0x5eedu, 0u};
-    philox4(c, seed);
+    unsigned c[4];
+    philox_block(c, ctr, 0x5eedu);
+    philox4x32_10(c, seed);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const float u = (float)(c[e] >> 8) * (1.0f / 16777216.0f);
+      const float u = philox_u01(c[e]);
       const float v = io<T>::ld(x, q * 4 + e);
       io<T>::st(y, q * 4 + e, u >= p ? v * scale : 0.f);
     }
@@ -251,14 +206,10 @@ __global__ void dropout_kernel(const T* __restrict__ x, T* __restrict__ y, int64
 }
 
 // ---- multi-scale attention blend (fp32, arbitrary 4-D strides) ------------------------------------------------
-struct S4 {
-  int64_t n, c, h, w;
-};
-
 __device__ __forceinline__ float sigmoidf_(float a) { return 1.f / (1.f + expf(-a)); }
 
-__global__ void att_blend_fwd_kernel(const float* __restrict__ lo, S4 ls, const float* __restrict__ hi, S4 hs,
-                                     const float* __restrict__ att, S4 as, float* __restrict__ out, int N, int C, int H,
+__global__ void att_blend_fwd_kernel(const float* __restrict__ lo, Strides4 ls, const float* __restrict__ hi, Strides4 hs,
+                                     const float* __restrict__ att, Strides4 as, float* __restrict__ out, int N, int C, int H,
                                      int W) {
   const int64_t total = (int64_t)N * C * H * W;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -274,8 +225,8 @@ __global__ void att_blend_fwd_kernel(const float* __restrict__ lo, S4 ls, const 
 }
 
 // one thread per pixel: glo = g*s, ghi = g*(1-s), gatt = sum_c (g*lo - g*hi) * (1-s)*s
-__global__ void att_blend_bwd_kernel(const float* __restrict__ g, S4 gs, const float* __restrict__ lo, S4 ls,
-                                     const float* __restrict__ hi, S4 hs, const float* __restrict__ att, S4 as,
+__global__ void att_blend_bwd_kernel(const float* __restrict__ g, Strides4 gs, const float* __restrict__ lo, Strides4 ls,
+                                     const float* __restrict__ hi, Strides4 hs, const float* __restrict__ att, Strides4 as,
                                      float* __restrict__ glo, float* __restrict__ ghi, float* __restrict__ gatt, int N,
                                      int C, int H, int W) {
   const int64_t total = (int64_t)N * H * W;
@@ -297,8 +248,6 @@ __global__ void att_blend_bwd_kernel(const float* __restrict__ g, S4 gs, const f
     if (gatt) gatt[i] = acc * sm * s;
   }
 }
-
-S4 s4(const int64_t* v) { return S4{v[0], v[1], v[2], v[3]}; }
 
 }  // namespace
 
@@ -502,7 +451,7 @@ extern "C" int ssseg_att_blend_fwd(const float* lo, const int64_t* lo_strides4_h
   const int64_t total = N * C * H * W;
   if (total == 0) return 0;
   hipLaunchKernelGGL(att_blend_fwd_kernel, dim3(ssseg_grid(total, 256, 1 << 16)), dim3(256), 0, (hipStream_t)stream,
-                     lo, s4(lo_strides4_host), hi, s4(hi_strides4_host), att, s4(att_strides4_host), out, (int)N, (int)C,
+                     lo, strides4(lo_strides4_host), hi, strides4(hi_strides4_host), att, strides4(att_strides4_host), out, (int)N, (int)C,
                      (int)H, (int)W);
   SSSEG_LAUNCH_CHECK();
   return 0;
@@ -518,8 +467,8 @@ extern "C" int ssseg_att_blend_bwd(const float* gout, const int64_t* g_strides4_
   const int64_t total = N * H * W;
   if (total == 0) return 0;
   hipLaunchKernelGGL(att_blend_bwd_kernel, dim3(ssseg_grid(total, 256, 1 << 16)), dim3(256), 0, (hipStream_t)stream,
-                     gout, s4(g_strides4_host), lo, s4(lo_strides4_host), hi, s4(hi_strides4_host), att,
-                     s4(att_strides4_host), glo, ghi, gatt, (int)N, (int)C, (int)H, (int)W);
+                     gout, strides4(g_strides4_host), lo, strides4(lo_strides4_host), hi, strides4(hi_strides4_host), att,
+                     strides4(att_strides4_host), glo, ghi, gatt, (int)N, (int)C, (int)H, (int)W);
   SSSEG_LAUNCH_CHECK();
   return 0;
 }

@@ -53,16 +53,13 @@ __device__ __forceinline__ int quant1(float x, float inv) {
   return (int)fminf(fmaxf(rintf(t), -127.f), 127.f);
 }
 
-template <typename T> struct Vec { static constexpr int V = 8; };
-template <> struct Vec<float> { static constexpr int V = 4; };
-
 // ---- observer ------------------------------------------------------------------------------------------------------
 // one thread per V-element group of a pixel's real channels; whole groups are one 16-byte load, the ragged tail and
 // rows whose stride breaks the alignment are read element by element; channels >= C are never read
 template <typename T>
 __global__ void __launch_bounds__(Q_THREADS) absmax_kernel(const T* __restrict__ x, int64_t P, int C, int64_t ldx,
                                                           bool aligned, float* __restrict__ slot) {
-  constexpr int V = Vec<T>::V;
+  constexpr int V = Vec16<T>::V;
   __shared__ float scratch[Q_THREADS / 64];
   const int groups = (C + V - 1) / V;
   const int64_t total = P * groups;
@@ -91,7 +88,7 @@ template <typename T>
 __global__ void __launch_bounds__(Q_THREADS) quantize_kernel(const T* __restrict__ x, int64_t P, int C, int64_t ldx,
                                                             bool aligned, const float* __restrict__ slot,
                                                             int8_t* __restrict__ q, int64_t ldq) {
-  constexpr int V = Vec<T>::V;
+  constexpr int V = Vec16<T>::V;
   const int chunks = (int)(ldq / 16);
   const int64_t total = P * chunks;
   const float a = slot[0];
@@ -170,31 +167,6 @@ struct ConvI8 {
 // LDS image of a tile: rows of 64 bytes; the 16-byte chunk c of row r lies at chunk (c ^ ((r >> 2) & 3)), so the 16 rows
 // a ds_read_b128 of one k-chunk touches fall on 16 different 16-byte bank slots
 __device__ __forceinline__ int lds_off(int row, int chunk) { return row * CV_BK + ((chunk ^ ((row >> 2) & 3)) << 4); }
-
-template <typename TO> struct Out4;
-template <> struct Out4<float> {
-  __device__ __forceinline__ static void ld(const float* p, float (&v)[4]) {
-    const float4 q = *(const float4*)p;
-    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-  }
-  __device__ __forceinline__ static void st(float* p, const float (&v)[4]) {
-    *(float4*)p = make_float4(v[0], v[1], v[2], v[3]);
-  }
-};
-template <> struct Out4<bf16_t> {
-  __device__ __forceinline__ static void ld(const bf16_t* p, float (&v)[4]) {
-    Chunk<bf16_t, 4>::cvt(Chunk<bf16_t, 4>::ld(p), v);
-  }
-  __device__ __forceinline__ static void st(bf16_t* p, const float (&v)[4]) {
-    const unsigned lo = (unsigned)f32_to_bf16(v[0]) | ((unsigned)f32_to_bf16(v[1]) << 16);
-    const unsigned hi = (unsigned)f32_to_bf16(v[2]) | ((unsigned)f32_to_bf16(v[3]) << 16);
-    *(uint2*)p = make_uint2(lo, hi);
-  }
-};
-template <> struct Out4<f16_t> {
-  __device__ __forceinline__ static void ld(const f16_t* p, float (&v)[4]) { H16::ld4(p, v); }
-  __device__ __forceinline__ static void st(f16_t* p, const float (&v)[4]) { H16::st4(p, v); }
-};
 
 // 256 threads = 2 (pixel halves of 64) x 2 (channel halves of 16 * TN) waves; a wave owns TN x 4 MFMA tiles.
 // BN = 32 * TN output channels per workgroup.
@@ -309,14 +281,14 @@ __global__ void __launch_bounds__(Q_THREADS) conv_i8_kernel(const int8_t* __rest
       const int64_t m = m0 + wm * 64 + 16 * j + fr;
       if (m >= g.M) continue;
       float v[4], res[4] = {0.f, 0.f, 0.f, 0.f};
-      if (residual) Out4<TO>::ld(residual + m * g.ldr + nb, res);
+      if (residual) Vec<TO, 4>::ld(residual + m * g.ldr + nb, res);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float t = fmaf((float)acc[i][j][e], mul[e], sh[e]);
         if (residual) t = __fadd_rn(t, res[e]);
         v[e] = act_fwd(t, g.act, g.slope);
       }
-      Out4<TO>::st(y + m * g.ldy + nb, v);
+      Vec<TO, 4>::st(y + m * g.ldy + nb, v);
     }
   }
 }

@@ -22,16 +22,6 @@ constexpr int SW_MAX_WINDOWS = 64;
 constexpr int SW_MAX_C = 64;
 constexpr int SW_MIRROR = 1, SW_NULL = 2;
 
-struct Strides {
-  int64_t n, c, h, w;
-};
-
-static Strides make_strides(const int64_t* s4) {
-  Strides s;
-  s.n = s4[0]; s.c = s4[1]; s.h = s4[2]; s.w = s4[3];
-  return s;
-}
-
 // the coordinate rule of ssseg_bilinear_fwd for align_corners=False (interp.hip src_index): source taps i0, i1 and
 // their weights l0, l1 for output index d
 struct Axis {
@@ -66,10 +56,10 @@ __device__ __forceinline__ float lerp2(float x00, float x01, float x10, float x1
 // ---- gather --------------------------------------------------------------------------------------------------------
 // grid (x: blocks of crop pixels, y: window).  T is the raw element (4 or 2 bytes): values are moved, not converted.
 template <typename T>
-__global__ void __launch_bounds__(SW_THREADS) window_gather_kernel(const T* __restrict__ img, Strides is, int B,
+__global__ void __launch_bounds__(SW_THREADS) window_gather_kernel(const T* __restrict__ img, Strides4 is, int B,
                                                                    int Cimg, int Hs, int Ws,
                                                                    const int* __restrict__ win, int ch, int cw,
-                                                                   T* __restrict__ out, Strides os) {
+                                                                   T* __restrict__ out, Strides4 os) {
   const int j = blockIdx.y;
   const int p = blockIdx.x * SW_THREADS + threadIdx.x;
   if (p >= ch * cw) return;
@@ -90,7 +80,7 @@ __global__ void __launch_bounds__(SW_THREADS) window_gather_kernel(const T* __re
 // window of this call covers is not touched.  IDENT: the logits are at the crop's own resolution (taps (1, 0): the
 // values themselves).
 template <int CMAX, bool IDENT>
-__global__ void __launch_bounds__(SW_THREADS) window_accumulate_kernel(const float* __restrict__ logits, Strides ls,
+__global__ void __launch_bounds__(SW_THREADS) window_accumulate_kernel(const float* __restrict__ logits, Strides4 ls,
                                                                        Axis ah, Axis aw, const int* __restrict__ win,
                                                                        int n, int C, int ch, int cw, int activation,
                                                                        int weighting, float* __restrict__ acc,
@@ -234,7 +224,7 @@ __global__ void __launch_bounds__(SW_THREADS) window_argmax_kernel(const float* 
 }
 
 template <int CMAX>
-void launch_accumulate(dim3 grid, hipStream_t st, bool ident, const float* logits, Strides ls, Axis ah, Axis aw,
+void launch_accumulate(dim3 grid, hipStream_t st, bool ident, const float* logits, Strides4 ls, Axis ah, Axis aw,
                        const int* win, int n, int C, int ch, int cw, int activation, int weighting, float* acc,
                        float* wsum, int Ha, int Wa) {
   if (ident)
@@ -260,7 +250,7 @@ extern "C" int ssseg_window_gather(const void* image, const int64_t* image_strid
   if (!frame_ok(B, Hs, Ws) || !frame_ok(1, ch, cw) || Cimg < 1 || Cimg > SW_MAX_C || n < 1 || n > 65535)
     return SSSEG_EINVAL;
   if (dt != SSSEG_F32 && dt != SSSEG_BF16 && dt != SSSEG_F16) return SSSEG_EINVAL;
-  const Strides is = make_strides(image_strides4), os = make_strides(crop_strides4);
+  const Strides4 is = strides4(image_strides4), os = strides4(crop_strides4);
   const dim3 grid((unsigned)((ch * cw + SW_THREADS - 1) / SW_THREADS), (unsigned)n);
   hipStream_t st = (hipStream_t)stream;
   if (dt == SSSEG_F32)
@@ -287,7 +277,7 @@ extern "C" int ssseg_window_accumulate(const float* logits, const int64_t* logit
     if (r[3] & SW_NULL) continue;
     if (r[0] < 0 || r[0] >= B || r[1] < 0 || r[1] + ch > Ha || r[2] < 0 || r[2] + cw > Wa) return SSSEG_EINVAL;
   }
-  const Strides ls = make_strides(logit_strides4);
+  const Strides4 ls = strides4(logit_strides4);
   const Axis ah = make_axis(h, ch), aw = make_axis(w, cw);
   const dim3 grid((unsigned)((Wa + SW_THREADS - 1) / SW_THREADS), (unsigned)Ha, (unsigned)B);
   const bool ident = h == ch && w == cw;

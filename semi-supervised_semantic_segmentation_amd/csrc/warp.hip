@@ -14,12 +14,9 @@
 // same bits on every run and under graph replay.  The matrices live in device memory, so a captured step replays
 // whatever ssseg_affine_draw_dev drew last.
 #include "common.h"
+#include "philox.h"
 
 namespace {
-
-struct Strides {
-  int64_t n, c, h, w;
-};
 
 struct Taps {
   int x0, y0;
@@ -48,7 +45,7 @@ __device__ __forceinline__ Taps affine_taps(const float* __restrict__ m, int x, 
 template <typename T, typename I>
 __global__ void __launch_bounds__(256) affine_warp_fwd_kernel(const T* __restrict__ x, T* __restrict__ y,
                                                               const float* __restrict__ mats, int64_t total_, int C,
-                                                              int H, int W, int CL, Strides xs, Strides ys,
+                                                              int H, int W, int CL, Strides4 xs, Strides4 ys,
                                                               float* __restrict__ valid) {
   const I total = (I)total_;
   for (I i = (I)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (I)gridDim.x * blockDim.x) {
@@ -92,7 +89,7 @@ template <typename T, typename I>
 __global__ void __launch_bounds__(256) affine_warp_bwd_kernel(const T* __restrict__ gy, T* __restrict__ gx,
                                                               const float* __restrict__ mats,
                                                               const float* __restrict__ mats_inv, int64_t total_,
-                                                              int C, int H, int W, int CL, Strides gys, Strides gxs) {
+                                                              int C, int H, int W, int CL, Strides4 gys, Strides4 gxs) {
   const I total = (I)total_;
   for (I i = (I)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (I)gridDim.x * blockDim.x) {
     const int cl = (int)(i % CL);
@@ -137,14 +134,6 @@ __global__ void __launch_bounds__(256) affine_warp_bwd_kernel(const T* __restric
   }
 }
 
-__device__ __forceinline__ void philox_round(unsigned (&c)[4], unsigned k0, unsigned k1) {
-  const unsigned M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
-  unsigned hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0];
-  unsigned hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
-  unsigned n0 = hi1 ^ c[1] ^ k0, n1 = lo1, n2 = hi0 ^ c[3] ^ k1, n3 = lo0;
-  c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
-
 // A(theta, s) and its inverse A(-theta, 1/s), built in fp64 and rounded once
 __device__ __forceinline__ void affine_store(float* m, double al, double be, double cx, double cy) {
   m[0] = (float)al;
@@ -164,16 +153,10 @@ __global__ void __launch_bounds__(256) affine_draw_kernel(float* mats, float* ma
   const uint64_t offset = (uint64_t)*offset_dev;
   const double cx = 0.5 * (double)(W - 1), cy = 0.5 * (double)(H - 1);
   for (int b = threadIdx.x; b < B; b += blockDim.x) {
-    const uint64_t ctr = offset + (uint64_t)b;
-    unsigned c[4] = {(unsigned)ctr, (unsigned)(ctr >> 32), 2u, 0u};
-    unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-      philox_round(c, k0, k1);
-      k0 += 0x9E3779B9u;
-      k1 += 0xBB67AE85u;
-    }
-    const float u1 = (float)(c[0] >> 8) * (1.0f / 16777216.0f), u2 = (float)(c[1] >> 8) * (1.0f / 16777216.0f);
+    unsigned c[4];
+    philox_block(c, offset + (uint64_t)b, 2u);
+    philox4x32_10(c, seed);
+    const float u1 = philox_u01(c[0]), u2 = philox_u01(c[1]);
     const float theta = max_angle * (2.f * u1 - 1.f);
     const float s = fminf(fmaxf(lo + u2 * (hi - lo), lo), hi);
     const double th = (double)theta * (3.14159265358979323846 / 180.0);
@@ -185,17 +168,8 @@ __global__ void __launch_bounds__(256) affine_draw_kernel(float* mats, float* ma
   if (threadIdx.x == 0) *offset_dev = (unsigned long long)(offset + (uint64_t)B);
 }
 
-Strides strides_of(const int64_t* s) {
-  Strides r;
-  r.n = s[0];
-  r.c = s[1];
-  r.h = s[2];
-  r.w = s[3];
-  return r;
-}
-
 // channel lanes per pixel: the channels of a channels-last tensor are its fastest axis
-int channel_lanes(int64_t C, const Strides& a, const Strides& b) {
+int channel_lanes(int64_t C, const Strides4& a, const Strides4& b) {
   if (C < 2 || a.c != 1 || b.c != 1) return 1;
   int cl = 1;
   while (cl < C && cl < 64) cl *= 2;
@@ -216,7 +190,7 @@ extern "C" int ssseg_affine_warp_fwd(const void* x, void* y, const float* mats, 
   if (!warp_args_ok(x, y, mats, N, C, H, W, x_strides4_host, y_strides4_host)) return SSSEG_EINVAL;
   if (dt != SSSEG_F32 && dt != SSSEG_BF16 && dt != SSSEG_F16) return SSSEG_EUNSUPPORTED;
   if (N == 0 || (C == 0 && !valid_out)) return 0;
-  const Strides xs = strides_of(x_strides4_host), ys = strides_of(y_strides4_host);
+  const Strides4 xs = strides4(x_strides4_host), ys = strides4(y_strides4_host);
   const int cl = channel_lanes(C, xs, ys);
   const int64_t total = N * H * W * cl;
   const bool i32 = total < 0x7fffffffLL - (1LL << 24);   // i + grid stride stays in int range
@@ -247,7 +221,7 @@ extern "C" int ssseg_affine_warp_bwd(const void* gy, void* gx, const float* mats
   if (!warp_args_ok(gy, gx, mats, N, C, H, W, gy_strides4_host, gx_strides4_host) || !mats_inv) return SSSEG_EINVAL;
   if (dt != SSSEG_F32 && dt != SSSEG_BF16 && dt != SSSEG_F16) return SSSEG_EUNSUPPORTED;
   if (N == 0 || C == 0) return 0;
-  const Strides gys = strides_of(gy_strides4_host), gxs = strides_of(gx_strides4_host);
+  const Strides4 gys = strides4(gy_strides4_host), gxs = strides4(gx_strides4_host);
   const int cl = channel_lanes((C + 3) / 4, gys, gxs);
   const int64_t total = N * H * W * cl;
   const bool i32 = total < 0x7fffffffLL - (1LL << 24);

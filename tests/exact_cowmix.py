@@ -3,7 +3,7 @@ test_cowmix_exact*.py).  Nothing here imports ssseg: the comparison functions ta
 of host arrays (`run`), so the host file can feed them a model's or a mutant's output instead.
 
 ssseg_cowmix_mask leaves every intermediate where the caller can read it: K, the taps, the vertical pass and the
-statistics in the workspace (carve, cowmix.hip:27-41: stats[B][2] f64, K in 16 bytes, taps[B][1023] f32, tmp[B][H][W]
+statistics in the workspace (carve, cowmix.hip: stats[B][2] f64, K in 16 bytes, taps[B][1023] f32, tmp[B][H][W]
 f32, thr[B] f32, each aligned to 16 bytes), the field and the threshold in field_out / thr_out.  Each stage is checked
 against ITS OWN inputs as the device produced them.
 
@@ -41,11 +41,11 @@ from oracle import cowmix_ref
 F32 = np.float32
 LD = np.longdouble
 U24, U53 = 2.0 ** -24, 2.0 ** -53
-KCAP, KC = 1023, 128            # cowmix.hip:14-15
-VT = (64, 64)                   # vertical pass tile: rows, columns (cowmix.hip:76-81)
-HT = (8, 256)                   # horizontal pass tile (cowmix.hip:132-137)
+KCAP, KC = 1023, 128            # cowmix.hip: KCAP, KC
+VT = (64, 64)                   # vertical pass tile: rows, columns (cowmix_vblur_kernel, VTH)
+HT = (8, 256)                   # horizontal pass tile (cowmix_hblur_kernel, HROWS x HTW)
 SWEEP = 4096 * 256              # pixels one sweep of the threshold kernel covers
-SQRT2_F = F32(1.41421354)       # cowmix.hip:228
+SQRT2_F = F32(1.41421354)       # cowmix_finalize_kernel
 FLT_MIN = 2.0 ** -126
 TAPS_MARGIN, ERFINV_MARGIN = 4.0, 4.0
 P_CYCLE = (0.5, 0.3, 0.7)
@@ -80,7 +80,7 @@ def _a16(x):
 
 
 def carve(B, H, W):
-    """carve (cowmix.hip:27-41): name -> (byte offset, dtype, shape), and the total"""
+    """carve (cowmix.hip): name -> (byte offset, dtype, shape), and the total"""
     out, off = {}, 0
     out['stats'] = (off, np.float64, (B, 2))
     off = _a16(off + 8 * 2 * B)
@@ -231,7 +231,8 @@ def check_taps(run, sigmas, what):
 # ---------------------------------------------------------------------------------------------------------------------
 def blur_restate(src, taps, K, axis, descending=False):
     """out = sum_k g[k] * in[. - K // 2 + k] along `axis` (1: rows, 2: columns) as the kernels form it
-    (cowmix.hip:113, 119, 182, 191): acc = fmaf(g[k], in, acc), k ascending from acc = 0, zero outside the image,
+    (the tap loops of cowmix_vblur_kernel and cowmix_hblur_kernel): acc = fmaf(g[k], in, acc), k ascending from acc = 0,
+    zero outside the image,
     per-sample taps [B, >= K]"""
     src = np.asarray(src, F32)
     B, H, W = src.shape
@@ -286,7 +287,7 @@ def erfinv_m():
 
 
 def thr_restate(stats, p, n, biased=False):
-    """cowmix_finalize_kernel (cowmix.hip:217-233) on the host in the kernel's precisions, erfinvf taken as scipy's
+    """cowmix_finalize_kernel (cowmix.hip) on the host in the kernel's precisions, erfinvf taken as scipy's
     erfinv rounded to fp32 (a model for the host file; the GPU comparison uses thr_reference)"""
     from scipy.special import erfinv
     s1, s2 = stats[:, 0], stats[:, 1]

@@ -24,8 +24,8 @@ from test_losses_ext_host import (bce64, binary_entropy64, ce64, dice_logits64, 
 F64 = torch.float64
 
 # ---- the launch geometry, as literals (the tests do not parse the kernels) ---------------------------------------
-RED_SPAN = 256 * 1024     # seglosses.hip:14-15 / eltwise.hip:10-11: RED_THREADS * RED_BLOCKS, one round of a reduction
-GRID_SPAN = 256 * 4096    # common.h:191: 256 threads * the default grid cap of ssseg_grid
+RED_SPAN = 256 * 1024     # seglosses.hip / eltwise.hip: RED_THREADS * RED_BLOCKS, one round of a reduction
+GRID_SPAN = 256 * 4096    # common.h ssseg_grid_cap(): 256 threads * the default grid cap of ssseg_grid
 PLANE_SPAN = 256 * 64     # seglosses.hip:17: RED_THREADS * PLANE_CHUNKS, one round of a per-plane reduction
 PLANE_BWD_SPAN = 256 * 256  # seglosses.hip:877,931: nfl_bwd / dicep_bwd launch at most 256 blocks per plane
 FINAL_SPAN = 256 * 256    # the *_final kernels loop nparts = ceil(n / 256) over 256 threads: second round at n > 65,536

@@ -26,7 +26,7 @@ F32, F64 = np.float32, np.float64
 # launch thresholds of csrc/lovasz.hip (line numbers of that file) and csrc/common.h, by the names used there
 TILE = 2048               # :28 `constexpr int TILE = LT * ITEMS`: one block of hist / scatter / grad
 SCAN_ROUND = 64           # :100 seg_rowscan_kernel `t0 += 64`; :696 gen_segsum, :270 lovasz_final_kernel `t += 64`
-GRID_SPAN = 256 * 16 * 256     # common.h:191 ssseg_grid_cap() 256 * 16 blocks, of 256 threads: prep / bwd / softmax-bwd
+GRID_SPAN = 256 * 16 * 256     # common.h ssseg_grid_cap(): 256 * 16 blocks, of 256 threads: prep / bwd / softmax-bwd
 COUNT_SPAN = 64 * 256     # :871 gen_core: lovasz_gen_count_kernel on at most 64 blocks of 256 per group
 COUNT_CAP = 64 * 16 * 256      # :870 cblocks = ceil(L / (256 * 16)) capped at 64: more than 16 rounds per block above
 FINAL_GROUPS = 256        # :709 lovasz_gen_final_kernel `g += 256`

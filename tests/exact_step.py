@@ -138,11 +138,12 @@ def _randn(g, *shape):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# 2. layout and dtype converters (eltwise.hip:13-71, 363-456)
+# 2. layout and dtype converters (eltwise.hip: the nchw_to_nhwc / nhwc_to_nchw / cast kernels and their entry points)
 # ---------------------------------------------------------------------------------------------------------------------
 DTYPES = ('f32', 'bf16', 'f16')
 DT_CODE = {'f32': 0, 'bf16': 1, 'f16': 2}   # native.F32 / BF16 / F16
-# the pairs each entry point dispatches (eltwise.hip:388-403, 415-430, 440-453); bf16 <-> f16 is refused by all three
+# the pairs each entry point dispatches (ssseg_nchw_to_nhwc, ssseg_nhwc_to_nchw, ssseg_cast in eltwise.hip); bf16 <-> f16
+# is refused by all three
 TO_NHWC_PAIRS = (('f32', 'f32'), ('f32', 'bf16'), ('bf16', 'bf16'), ('bf16', 'f32'), ('f32', 'f16'), ('f16', 'f16'),
                  ('f16', 'f32'))
 TO_NCHW_PAIRS = TO_NHWC_PAIRS
@@ -203,7 +204,8 @@ def values(shape, dt_in, key='v', lanes=None):
 
 
 def to_nhwc_ref(x, Cp, dt_out):
-    """[N, C, H, W] -> [N, H, W, Cp]: permute, one cast, +0.0 in the lanes c >= C (eltwise.hip:16-18, 53)"""
+    """[N, C, H, W] -> [N, H, W, Cp]: permute, one cast, +0.0 in the lanes c >= C (nchw_to_nhwc_kernel and
+    nchw_to_nhwc_pix_kernel, eltwise.hip)"""
     n, c, h, w = x.shape
     y = torch.zeros(n, h, w, Cp, dtype=TORCH_DTYPE[dt_out])
     y[..., :c] = x.permute(0, 2, 3, 1).float().to(TORCH_DTYPE[dt_out])
@@ -211,7 +213,7 @@ def to_nhwc_ref(x, Cp, dt_out):
 
 
 def to_nchw_ref(x, C, dt_out):
-    """[N, H, W, ldc] -> [N, C, H, W] of its first C lanes (eltwise.hip:62-63)"""
+    """[N, H, W, ldc] -> [N, C, H, W] of its first C lanes (nhwc_to_nchw_kernel, eltwise.hip)"""
     return x[..., :C].permute(0, 3, 1, 2).float().to(TORCH_DTYPE[dt_out]).contiguous()
 
 
@@ -237,7 +239,7 @@ def to_nhwc_mutant(x, Cp, dt_out, kind, fill):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# 3. clip + SGD (eltwise.hip:219-250)
+# 3. clip + SGD (sgd_kernel, eltwise.hip)
 # ---------------------------------------------------------------------------------------------------------------------
 SGD_LR, SGD_N, SGD_S = 0.05, 1027, 1024.0
 SGD_MOM, SGD_WD, SGD_CLIP, SGD_AMP = (0.0, 0.9), (0.0, 5e-4), ('off', 'above', 'below'), (False, True)
@@ -246,7 +248,7 @@ SGD_COEF_K = 6
 
 
 def sgd_ref(p, g, buf, coef, lr, mom, wd, first, want_shadow, contract=True):
-    """sgd_kernel's loop body (eltwise.hip:232-248) given the scalar coefficient it applied:
+    """sgd_kernel's loop body (eltwise.hip) given the scalar coefficient it applied:
         gi = g * coef                       (written back to g)
         d  = fma(p, wd, gi) if wd != 0 else gi
         b  = d if first else fma(buf, mom, d)   (only when mom != 0, else b = d and buf is not touched)
@@ -274,8 +276,8 @@ def sgd_ref(p, g, buf, coef, lr, mom, wd, first, want_shadow, contract=True):
 
 
 def clip_coef_ref(sq, max_norm, unscale):
-    """the coefficient of sgd_kernel (eltwise.hip:222-230) in fp64: unscale * min(max_norm / (sqrt(sq) unscale +
-    1e-6), 1), unscale alone without a clip"""
+    """the coefficient of sgd_kernel (eltwise.hip, the lines before its loop) in fp64: unscale * min(max_norm /
+    (sqrt(sq) unscale + 1e-6), 1), unscale alone without a clip"""
     sq, max_norm, unscale = float(sq), float(max_norm), float(unscale)
     if max_norm <= 0:
         return unscale
@@ -318,7 +320,7 @@ def sgd_max_norm(op, clip):
 def sgd_check(got, op, mom, wd, max_norm, amp, first, what):
     """got: the device's p, g, buf (None when mom == 0), shadow bits (None when not asked for).
     (a) The coefficient the device applied, c = g'[0] / S (exact: S is a power of two and g[0] = S), is held to
-    clip_coef_ref of the fp64 squared norm within SGD_COEF_K 2^-24 relative.  Counted from eltwise.hip:228-229: the
+    clip_coef_ref of the fp64 squared norm within SGD_COEF_K 2^-24 relative.  Counted from sgd_kernel's clip block: the
     fp32 rounding of the accumulated norm (1/2 after the root; counted 1, which also covers the summation order of the
     fp64 accumulation), sqrtf, * coef, + 1e-6f, the division, the final * coef: k = 6 (a contraction removes one).
     (b) With c, every element of p', g', buf' and the shadow equals sgd_ref bit for bit, the planted one included."""
@@ -364,7 +366,7 @@ def sgd_device_model(op, mom, wd, max_norm, amp, first, shadow, mutate=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# 4. squared norm (eltwise.hip:199-216)
+# 4. squared norm (sq_partial_kernel, sq_final_kernel, eltwise.hip)
 # ---------------------------------------------------------------------------------------------------------------------
 SQ_SIZES = (1, 63, 65, 257, SWEEP_RED + 7)
 
@@ -397,7 +399,7 @@ def sq_check_bounded(out, x, what):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# 5. EMA (eltwise.hip:181-196, 525-534)
+# 5. EMA (ema_kernel, ssseg_ema_update, eltwise.hip)
 # ---------------------------------------------------------------------------------------------------------------------
 # the last: ssseg_grid(n / 4 + 1, 256, 2048) caps at 2048 * 256 threads, so the float4 loop takes a second iteration
 # only when n / 4 > 2048 * 256: one float4 of a second sweep and a 3-element tail (SWEEP_EMA + 3 is still one sweep)
@@ -406,7 +408,7 @@ EMA_ALPHAS = (0.99, 0.999)
 
 
 def ema_ref(e, p, alpha, mutate=None):
-    """a = float32(alpha), beta = float32(1.0 - alpha) with the subtraction in fp64 (ssseg_ema_update, eltwise.hip:529);
+    """a = float32(alpha), beta = float32(1.0 - alpha) with the subtraction in fp64 (ssseg_ema_update, eltwise.hip);
     e' = fma(p, beta, e * a) (:188).  mutate='beta32': beta = float32(1) - float32(alpha)."""
     a = F32(alpha)
     beta = F32(1.0) - a if mutate == 'beta32' else F32(1.0 - float(alpha))
@@ -424,7 +426,7 @@ def ema_check(got, e, p, alpha, what):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# 6. loss scale (eltwise.hip:266-292)
+# 6. loss scale (amp_update_kernel, scale_by_kernel, eltwise.hip)
 # ---------------------------------------------------------------------------------------------------------------------
 AMP_INIT, AMP_BACKOFF, AMP_INTERVAL = 8.0, 0.5, 3
 AMP_GROWTHS = (2.0, 1.5)
@@ -447,7 +449,7 @@ def amp_initial(scale=AMP_INIT):
 
 
 def amp_ref(state, sq, growth, backoff, interval):
-    """amp_update_kernel (eltwise.hip:266-285) in float32: state = [scale, growth tracker, found_inf, 1 / scale]"""
+    """amp_update_kernel (eltwise.hip) in float32: state = [scale, growth tracker, found_inf, 1 / scale]"""
     st = np.array(state, dtype=np.float32)
     sc, growth, backoff = st[0], F32(growth), F32(backoff)
     if not np.isfinite(F32(sq)):
@@ -474,7 +476,7 @@ def amp_script(growth):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# 7. axpby, scale (eltwise.hip:287-305)
+# 7. axpby, scale (axpby_kernel, scale_kernel, eltwise.hip)
 # ---------------------------------------------------------------------------------------------------------------------
 AXPBY_N = (1, 257, 2 ** 20 + 5)
 AXPBY_AB = ((1.0, 1.0), (0.5, 10.0), (-0.3, 0.7))
@@ -483,7 +485,7 @@ SCALE_F32_N = (1, SWEEP_SGD + 5)
 
 
 def axpby_ref(x, a, y=None, b=0.0):
-    """out = fma(a, x, b * y), or a * x without y (axpby_kernel, eltwise.hip:299)"""
+    """out = fma(a, x, b * y), or a * x without y (axpby_kernel, eltwise.hip)"""
     x = np.asarray(x, F32)
     if y is None:
         return x * F32(a)
@@ -501,7 +503,7 @@ def vec(n, key):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# 8. sigmoid (eltwise.hip:73, 252-263)
+# 8. sigmoid (sigmoidf_ref, sigmoid_fwd_kernel, sigmoid_bwd_kernel, eltwise.hip)
 # ---------------------------------------------------------------------------------------------------------------------
 SIGMOID_N = (4099, SWEEP_DEFAULT + 5)
 SIGMOID_SPECIALS = (0.0, 20.0, -20.0, 90.0, -90.0, INF, -INF)
@@ -525,7 +527,7 @@ def sigmoid_overflows(x):
 
 
 def sigmoid_check_fwd(got, x, what):
-    """y = 1 / (1 + expf(-x)) (sigmoidf_ref, eltwise.hip:73).  k = SIGMOID_K_FWD = 4, the count att_blend_random
+    """y = 1 / (1 + expf(-x)) (sigmoidf_ref, eltwise.hip).  k = SIGMOID_K_FWD = 4, the count att_blend_random
     documents for the same expression: expf within 1 ulp (2), the sum (1), the division (1); a relative error of e =
     exp(-x) reaches y scaled by e / (1 + e) < 1, so M = |ref|.  Exactly 0, 1 and 1/2 at -inf, +inf and 0.  Where
     expf(-x) overflows (sigmoid_overflows) the documented result is exactly +0.0."""
@@ -543,7 +545,7 @@ def sigmoid_check_fwd(got, x, what):
 
 
 def sigmoid_check_bwd(got, v, gy, what):
-    """gx = gy * (v * (1 - v)) (sigmoid_bwd_kernel, eltwise.hip:260-261) with v the stored forward output:
+    """gx = gy * (v * (1 - v)) (sigmoid_bwd_kernel, eltwise.hip) with v the stored forward output:
     1 - v, v * (...), gy * (...): k = SIGMOID_K_BWD = 3 against M = |gy v (1 - v)| in fp64 on the stored v"""
     v64, g64 = torch.from_numpy(v.astype(np.float64)), torch.from_numpy(gy.astype(np.float64))
     ref = g64 * (v64 * (1.0 - v64))
@@ -551,7 +553,7 @@ def sigmoid_check_bwd(got, v, gy, what):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# 9. mix (cowmix.hip:311-319)
+# 9. mix (mix_kernel, cowmix.hip)
 # ---------------------------------------------------------------------------------------------------------------------
 MIX_SHAPES = ((2, 3, 5, 7), (2, 3, 419, 419))   # 210 elements; 1 053 366 > SWEEP_DEFAULT
 MIX_K = 3
@@ -586,7 +588,7 @@ def mix_check_binary(got, a, b, m, what):
 
 
 def mix_check_soft(got, a, b, m, mode, what):
-    """v = a m + b (1 - m) (mix_kernel, cowmix.hip:316) in fp32 from the stored a, b, rounded once to the storage
+    """v = a m + b (1 - m) (mix_kernel, cowmix.hip) in fp32 from the stored a, b, rounded once to the storage
     dtype: the roundings are 1 - m, two products and the sum; the error of 1 - m reaches the element times |b|, each
     product's its own term, the sum's at most |a| m + |b| (1 - m): together under MIX_K = 3 times 2^-24 (|a| + |b|)
     (a contraction removes one, never adds)."""

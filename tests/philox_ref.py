@@ -1,8 +1,8 @@
 """Host restatement (numpy) of every device-side random draw, for tests/test_device_rng.py and
 tests/test_device_rng_host.py.
 
-The five separately compiled copies of Philox-4x32-10 (csrc/cowmix.hip, warp.hip, mixmask.hip, pool.hip, augment.hip)
-are the standard generator (the published known-answer vectors, tests/test_device_rng_host.py): counter
+The one device Philox-4x32-10 (philox4x32_10 in csrc/philox.h, compiled into cowmix.hip, warp.hip, mixmask.hip, pool.hip
+and augment.hip) is the standard generator (the published known-answer vectors, tests/test_device_rng_host.py): counter
 (c0, c1, c2, c3) = (ctr mod 2^32, ctr >> 32, word2, word3) with ctr taken mod 2^64, key (seed mod 2^32, seed >> 32),
 ten rounds, the key bumped by (0x9E3779B9, 0xBB67AE85) after each.  `philox` is that function, vectorised over the
 counters; one function per consumer restates the layout (which counter and which word feeds which output) and the fp32

@@ -238,7 +238,7 @@ def test_sgd_operands():
             assert np.isfinite(F32(op['sq'])) and op['norm'] >= 1.0
             for k in ('p', 'g', 'buf'):
                 assert (op[k] != 0).mean() >= 0.5 and (n < 8 or len(np.unique(op[k])) > n // 2)
-    # the grid-sweep constants are those of the launches (common.h ssseg_grid, eltwise.hip:530, 555)
+    # the grid-sweep constants are those of the launches (ssseg_grid; ssseg_ema_update, ssseg_sgd_step)
     assert S.SGD_SIZES[-1] > S.SWEEP_SGD and S.SQ_SIZES[-1] > S.SWEEP_RED
     # the EMA's float4 loop runs n // 4 items on at most SWEEP_EMA // 4 threads: a second iteration needs more items
     assert S.EMA_SIZES[-1] // 4 > S.SWEEP_EMA // 4 and S.EMA_SIZES[-1] % 4 == 3
