@@ -12,21 +12,36 @@
 //   ssseg_aug_blur       separable Gaussian (GaussianBlur; the ElasticTransform displacement fields)
 //   ssseg_aug_iso_finish ISONoise (HLS hue / luminance noise, per-image luminance std) and ToFloat -> NCHW [0, 1]
 // albumentations and cv2 are absent from this image: parity with them is unpinned; the kernels are checked against
-// the numpy restatement in oracle/augment_ref.py (tests/test_augment.py).
+// the numpy restatement in oracle/augment_ref.py (tests/test_augment.py; per pixel in tests/test_augment_exact.py).
 #include "common.h"
 #include "philox.h"
 
 namespace {
 
 // reflect-101 (OpenCV BORDER_REFLECT_101: ... c b | a b c ... | d c ...) and scipy 'reflect' (... b a | a b ...)
+// Closed form (one modulo by the period, unsigned so that INT_MIN folds too): the cost does not grow with the distance
+// of i from the image.  n < 2^30.
 __device__ __forceinline__ int reflect101(int i, int n) {
+  if ((unsigned)i < (unsigned)n) return i;
   if (n == 1) return 0;
-  while ((unsigned)i >= (unsigned)n) i = i < 0 ? -i : 2 * n - 2 - i;
-  return i;
+  const unsigned period = 2u * (unsigned)n - 2u;
+  const unsigned j = (i < 0 ? 0u - (unsigned)i : (unsigned)i) % period;
+  return (int)(j >= (unsigned)n ? period - j : j);
 }
 __device__ __forceinline__ int reflect_sym(int i, int n) {
-  while ((unsigned)i >= (unsigned)n) i = i < 0 ? -i - 1 : 2 * n - 1 - i;
-  return i;
+  if ((unsigned)i < (unsigned)n) return i;
+  const unsigned period = 2u * (unsigned)n;
+  const unsigned j = (i < 0 ? ~(unsigned)i : (unsigned)i) % period;   // ~i = -i - 1
+  return (int)(j >= (unsigned)n ? period - 1u - j : j);
+}
+
+// Source coordinates are supported within +-2^30 (exact in fp32, and floor + 1 stays an int); anything beyond is
+// clamped there, which is outside every image (H * W * 3 < 2^31).  NaN: outside for the constant border, coordinate
+// 0 for reflect-101.
+constexpr float kCoordMax = 1073741824.f;
+__device__ __forceinline__ float finite_coord(float s, int border) {
+  if (!(s == s)) return border == 1 ? 0.f : -kCoordMax;
+  return fminf(fmaxf(s, -kCoordMax), kCoordMax);
 }
 
 __device__ __forceinline__ float clamp255(float v) { return fminf(fmaxf(v, 0.f), 255.f); }
@@ -63,7 +78,8 @@ __global__ void aug_warp_kernel(const uint8_t* __restrict__ img, const uint8_t* 
   const ssseg_aug_warp_params p = params[n];
   float qx, qy;
   distort(p, x, y, Wo, Ho, gmaps, fields, n, qx, qy);
-  const float sx = p.a[0] * qx + p.a[1] * qy + p.a[2], sy = p.a[3] * qx + p.a[4] * qy + p.a[5];
+  const float sx = finite_coord(p.a[0] * qx + p.a[1] * qy + p.a[2], p.border);
+  const float sy = finite_coord(p.a[3] * qx + p.a[4] * qy + p.a[5], p.border);
   const int64_t opix = ((int64_t)n * Ho + y) * Wo + x, plane = (int64_t)Ho * Wo;
   // image: bilinear (cv2.INTER_LINEAR), border reflect-101 or constant 0
   const float fx0 = floorf(sx), fy0 = floorf(sy);
